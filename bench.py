@@ -39,8 +39,18 @@ Multi-GPU: the env batch shards embarrassingly (weak scaling, B per GPU fixed); 
 torch.distributed (RCCL) is used only for the barrier and the max-over-ranks of the elapsed time.
 
 Extra objects on the JSON line: "roofline" (dominant kernel: algorithmic bytes or flops per launch / kernel time from
-hipEvents on the launch stream) and "cpu_baseline" (the C oracle timed on the host cores on a bounded sample, plus a
-reference-shaped one-env-at-a-time Python loop; rank 0, N=1 only).
+hipEvents on the launch stream of the timed region itself) and, with --full only, "cpu_baseline" (the C oracle timed on
+the host cores on a bounded sample, plus a reference-shaped one-env-at-a-time Python loop; rank 0, N=1 only).
+
+A plain run (no --full) does only what the headline needs: set up, warm up, time --steps steps, write the outputs if
+--dump-outputs is given, print the line.  --full adds the measurements that take runs of their own (today the CPU
+baseline; --no-cpu-baseline leaves it out again).
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the timed path computed in its last step -- the arrays a
+caller of that path receives (state x, observations, rewards, done flags, adaptive step counts; the trajectories for the
+rollout workloads; per segment for the mixed shard) -- as DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded
+sample of envs, the same for every array of a batch, when the outputs are larger: DIR/env_index.npy lists it).  The
+inputs are seeded: the same arguments give the same inputs from run to run.
 """
 import argparse
 import copy
@@ -478,6 +488,29 @@ def clock_preheat(torch, dev, ms):
     return (time.perf_counter() - t0) * 1e3
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: write [(name, tensor with the env axis last)] as out_dir/<name>.npy in float64.  When the arrays
+    (with the index file) would exceed `limit_bytes`, every array keeps the same fixed, seeded sample of its envs, listed
+    in env_index.npy.  Returns the names written."""
+    import numpy as np
+    import torch
+
+    B = int(arrays[0][1].shape[-1])
+    assert all(int(t.shape[-1]) == B for _, t in arrays), "one env count per dump"
+    os.makedirs(out_dir, exist_ok=True)
+    full = sum(8 * t.numel() for _, t in arrays)
+    if full > limit_bytes:
+        k = max(1, int(B * limit_bytes / (full + 8 * B)))
+        ix = torch.as_tensor(np.sort(np.random.default_rng(seed).choice(B, size=k, replace=False)))
+        arrays = [(n, t.index_select(t.dim() - 1, ix.to(t.device))) for n, t in arrays] + [("env_index", ix)]
+    for name, t in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float64).numpy())
+    return [n for n, _ in arrays]
+
+
 def self_launch(n):
     """`python3 bench.py --gpus N` without a launcher: re-run this command line as N ranks of ONE node under
     torch.distributed.run (the command the driver's contract names).  Returns the launcher's exit code."""
@@ -495,14 +528,18 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="cstr", choices=["cstr", "cstr_safe", "cstr_rollout", "cstr_safe_rollout", "cstr_unc", "four_tank", "me10", "me10_ros4", "me10_ros5", "me20", "cryst", "cryst_cv8", "mixed"])
     ap.add_argument("--batch", type=int, default=None, help="envs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline that take runs of their own (the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-all-legs", action="store_true",
                     help="cpu_baseline: also run the legs whose thread count is above the container's cgroup CPU quota")
     ap.add_argument("--cpu-threads", type=int, default=None, help="fixed OpenMP team of the cpu_baseline leg (default min(16, avail))")
@@ -528,7 +565,11 @@ def main():
                          "(default: the workload's named one)")
     ap.add_argument("--coop-thr", type=float, default=None,
                     help="me10_ros4 / mixed: threshold of the cooperative rule of the Rodas4 plan (0 = off; default: the plan's)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     # Round 6: HIP graphs are the default launch form of the single-model workloads too (the mixed shard's since round 4):
     # same kernels, same arguments, no launch-to-launch gaps -- measured on the headline 13.58 -> 12.50 us per step in the default
     # shape and 15.2 -> 14.5 in a 20-step region (profiles/r6/graph_default.txt).  --eager gives the plain launches.
@@ -849,6 +890,22 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, host_us = float(tt[0].item()), float(tt[1].item())
 
+    if args.dump_outputs and rank == 0:
+        # what the timed path computed in its last step, as its caller receives it (env axis last)
+        def env_outputs(e, prefix=""):
+            outs = [("x", e.x), ("obs", e.obs_soa), ("rew", e.rew), ("done", e.done)]
+            if e.nsteps is not None:
+                outs.append(("nsteps", e.nsteps))
+            return [(prefix + n, t) for n, t in outs]
+
+        if mixed:
+            dump = [a for e in envs for a in env_outputs(e, e.spec.model.name + "_")]
+        elif roll:
+            dump = [("traj_x", traj_x), ("traj_r", traj_r)]
+        else:
+            dump = env_outputs(env)
+        dump_outputs(args.dump_outputs, dump)
+
     # sanity: a fast kernel producing garbage is not a result.  Physical boxes, not just finiteness (a diverged RK4
     # yields finite values up to 1e91), and the per-env status byte of the last step.
     def sane(e):
@@ -1050,7 +1107,7 @@ def main():
                                        "first observation row)" if roll else "eager pcg_step launches" if not graphs else
                                        f"HIP graphs (pcg_graph_*) of the consecutive plain steps of an episode: {len(graphs)} recorded before "
                                        "the timed region; an episode's last step (same-launch reset) is a plain launch")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(spec, threads=args.cpu_threads, all_legs=args.cpu_all_legs)
         print(json.dumps(out), flush=True)
     for e in all_envs:

@@ -21,7 +21,7 @@ def _json_line(out):
 
 def test_single_rank_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "70", "--warmup", "11",
-                        "--preheat-ms", "20"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--preheat-ms", "20", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert KEYS <= set(d) and "cpu_baseline" in d
@@ -35,6 +35,44 @@ def test_single_rank_line():
     assert cb["reference_shaped"]["cores"] == 1 and cb["reference_shaped"]["value"] > 0
     assert rf["traffic_measured_in_run"] is False and d["config"]["workload"] == "cstr_b2^20_rk4_fp64"
     assert d["config"]["ranks_seen"] == 1
+
+
+@pytest.mark.parametrize("wl,batch,steps,names", [("cstr", 65536, 70, {"x", "obs", "rew", "done"}),
+                                                  ("cstr_rollout", 65536, 59, {"traj_x", "traj_r", "env_index"}),
+                                                  ("mixed", 30000, 59, {f"{m}_{n}" for m in ("cstr", "four_tank", "multistage_extraction")
+                                                                        for n in ("x", "obs", "rew", "done")}
+                                                   | {"multistage_extraction_nsteps"})])
+def test_plain_line_and_dumped_outputs(tmp_path, wl, batch, steps, names):
+    """A plain run (no --full) carries the headline and no CPU baseline; --dump-outputs writes what the timed path computed
+    in its last step (float64, at most 64 MB: the rollout's trajectories as a fixed sample of envs), and two runs with the
+    same arguments write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--batch", str(batch),
+                            "--steps", str(steps), "--warmup", "2", "--preheat-ms", "10", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert "cpu_baseline" not in d and d["steps"] == steps and d["config"]["sane"]
+        assert abs(d["value"] - d["config"]["global_envs"] * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+        files = sorted(out.glob("*.npy"))
+        assert {f.stem for f in files} == names
+        assert sum(f.stat().st_size for f in files) <= 64 * 10 ** 6 + 128 * len(files)  # + the .npy headers
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrs.values())
+        if wl == "cstr":  # the whole batch
+            assert arrs["x"].shape == (2, batch) and arrs["obs"].shape == (3, batch) and arrs["rew"].shape == (batch,)
+        elif wl == "cstr_rollout":  # trajectories (Nobs, N, B) / (1, N, B), sampled over the envs
+            k = arrs["env_index"].size
+            assert 0 < k < batch and arrs["traj_x"].shape == (3, 60, k) and arrs["traj_r"].shape == (1, 60, k)
+        else:  # every segment's envs, whole
+            assert all(a.shape[-1] == d["config"]["envs_per_gpu"] // 3 for a in arrs.values())
+        dumps.append(arrs)
+    for k in names:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 @pytest.mark.parametrize("wl,batch,steps", [("mixed", 30000, 8), ("mixed", 30000, 59), ("me10", 8192, 6), ("me10_ros4", 8192, 6), ("me10_ros5", 8192, 6), ("cryst", 8192, 6), ("cryst_cv8", 8192, 6), ("cstr_safe", 65536, 20), ("four_tank", 65536, 20),

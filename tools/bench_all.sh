@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd $ROOT
 [ -f gpurun_out/pmc.json ] && mkdir -p profiles/r6 && cp gpurun_out/pmc.json profiles/r6/pmc.json
 : > gpurun_out/bench_workloads.jsonl
 for w in cstr cstr_safe cstr_rollout cstr_safe_rollout cstr_unc four_tank me10 me10_ros4 me10_ros5 me20 cryst cryst_cv8 mixed; do
-  extra="--no-cpu-baseline"; [ $w = cstr ] && extra=""
+  extra="--no-cpu-baseline"; [ $w = cstr ] && extra="--full"
   python bench.py --workload $w $extra 2>/dev/null | grep '^{' | tail -1 >> gpurun_out/bench_workloads.jsonl
 done
 python - <<'PY' > gpurun_out/bench_all.txt

@@ -3,8 +3,8 @@
 set -u
 python -c "import torch"
 OUT=gpurun_out/evidence; mkdir -p $OUT
-for i in 1 2 3; do python bench.py 2>/dev/null | tail -1 >> $OUT/bench_runs.jsonl; done
-for w in four_tank me10 me20 cryst mixed; do python bench.py --workload $w 2>/dev/null | tail -1 >> $OUT/bench_workloads.jsonl; done
+for i in 1 2 3; do python bench.py --full 2>/dev/null | tail -1 >> $OUT/bench_runs.jsonl; done
+for w in four_tank me10 me20 cryst mixed; do python bench.py --workload $w --full 2>/dev/null | tail -1 >> $OUT/bench_workloads.jsonl; done
 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_driver_shape.json
 for w in cstr four_tank cryst; do PROF_PMC_STEPS=590 PROF_PMC_WARMUP=59 bash tools/prof.sh $w --workload $w > /dev/null 2>&1; done
 python - <<'PY'
