@@ -95,25 +95,29 @@ struct pcg_plan {
   int stream_bpc;    // PCG_OPT_STREAM_BLOCKS_PER_CU: 0 = occupancy query
   int nt_stores;     // PCG_OPT_NT_STORES
   int num_cus;
-  int stream_occ[2]; // resident workgroups per CU of the stream kernels [EPL-1] (0 = not queried yet)
+  // launch geometry of every persistent kernel the plan could take, settled at creation (plan_geometry)
+  int stream_occ[2]; // resident workgroups per CU of the stream kernels [EPL-1]
   int pipe_occ[2][2];  // [auto-reset instantiation][EPL-1]
-  int feat_occ[MAX_FEAT];  // resident workgroups per CU of the feature-masked kernels (0 = not queried yet)
-  int q_bpc[2], q_tile[2]; // work-queue kernel [per_env_t]: resident workgroups per CU, tile slots (0 = not chosen yet,
-                           // -1 = does not fit)
+  int feat_occ[MAX_FEAT];  // resident workgroups per CU of the feature-masked kernels
+  int q_bpc[2], q_tile[2]; // work-queue kernel [per_env_t]: resident workgroups per CU, tile slots (0 = no queue launch)
   int q_tile1[2];          // the largest tile with ONE workgroup per CU (Rodas4: launches that fit one tile per CU)
+  // reference paths the tests select through the environment, read at creation: PCG_NO_FIXUP (guarded plans in one
+  // launch), PCG_NO_FLAT (the single-kernel rollout), PCG_Q_FORCE_LEAN (the lean queue layout wherever it fits)
+  bool no_fixup, no_flat, q_force_lean;
   int64_t env_offset;
   DevConst hc;       // host copy
   DevConst* dC;      // device copy
   double* dsched;    // [nsp+nd][N]
-  size_t sched_bytes;
   LeanStep* dlean;   // [N] wave-uniform values of each lock-stepped step (inside the dsched allocation)
   int cfg_nu;        // na + ndm as the caller counts them
   hipFunction_t jit_fn[2];  // run-time compiled general step kernel with user expressions [per_env_t] (or null)
   hipFunction_t jit_integ, jit_rhs;  // PCG_MODEL_USER: the run-time compiled test hooks (pcg_integrate / pcg_rhs)
   hipFunction_t jit_roll;            // run-time compiled fused rollout of a plan with user expressions (or null)
   int nx;                   // states (the kernel table's for built-in models, the cfg's for PCG_MODEL_USER)
-  int32_t* flat_ws;         // work space of the barrier-free rollout (pcg_rollout_flat.hpp): 4 counters + 2 x flat_cap indices,
-  int64_t flat_cap;         // allocated at the first rollout that takes that path (and again if a later batch is larger)
+  // work space of the barrier-free rollout (pcg_rollout_flat.hpp): 4 counters + 2 x flat_cap indices, allocated at the first
+  // rollout that takes that path (and again if a later batch is larger) -- the only plan state a launch still writes
+  int32_t* flat_ws;
+  int64_t flat_cap;
 };
 static constexpr uint32_t PLAN_MAGIC = 0x50434731u;  // 'PCG1'
 
@@ -121,6 +125,11 @@ static constexpr uint32_t PLAN_MAGIC = 0x50434731u;  // 'PCG1'
   do {                                         \
     hipError_t _e = (expr);                    \
     if (_e != hipSuccess) return (int)_e;      \
+  } while (0)
+#define PCG_TRY(expr)                          \
+  do {                                         \
+    const int _rc = (expr);                    \
+    if (_rc != PCG_OK) return _rc;             \
   } while (0)
 
 // Kernel-instantiation coverage (test infrastructure; off unless PCG_COVERAGE is set in the environment when the library is
@@ -572,9 +581,6 @@ static uint64_t fnv1a_seed(const std::string& s, uint64_t seed) {
   for (unsigned char ch : s) h = (h ^ ch) * 1099511628211ull;
   return h;
 }
-#ifndef PCG_SRC_HASH
-#define PCG_SRC_HASH "unknown-build"  // the Makefile passes a digest of csrc/*.hpp, csrc/*.hip and include/pcgym_hip.h
-#endif
 
 // digest of the headers a run-time compilation will see: every *.hpp of the include directory and the ABI header
 // next to it (../../include/pcgym_hip.h), by content.  Cached per directory for the life of the process.
@@ -811,6 +817,127 @@ static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* o
   return PCG_E_JIT;
 }
 
+// ---- launch geometry ------------------------------------------------------------------------------------------
+// Dynamic LDS one workgroup may ask for, and the budget of the work-queue kernels' workgroups on one CU (2 KB below it)
+constexpr size_t LDS_MAX = 160 * 1024;
+constexpr size_t LDS_CU = LDS_MAX - 2048;
+
+static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+static bool al2(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 1u) == 0; }
+
+// the plan's schedule rows (set points, disturbances), as per-env-t kernels stage them in LDS
+static size_t sched_bytes(const DevConst& c) { return sizeof(double) * (size_t)(c.nsp + c.nd) * c.N; }
+// ... what a per-env-t launch stages behind `integ` bytes of the integrator's own LDS (0: they stay in HBM)
+static size_t sched_in_lds_bytes(const DevConst& c, size_t integ) {
+  const size_t sb = sched_bytes(c);
+  return sb > 0 && integ + sb <= (integ > 48 * 1024 ? LDS_MAX : 64 * 1024) ? sb : 0;
+}
+
+static bool lds_stages_on(const pcg_plan* p, const Kernels& k) {
+  return p->lds_stages && p->integrator_id == PCG_INT_DOPRI5 && k.has_lds_stages;
+}
+// workgroup size of the plan's one-env-per-lane kernels, and the dynamic LDS their integrator needs (*integ_lds)
+static int classic_shape(const pcg_plan* p, const Kernels& k, bool lds_st, size_t* integ_lds) {
+  const bool user = p->model_id == PCG_MODEL_USER, rstr = !user && k.ros_structured;  // Rodas4 with the model's own W: no LDS
+  const int knx = user ? p->nx : k.nx;  // the kernels' compile-time state count
+  *integ_lds = sizeof(double) * integ_lds_doubles(knx, p->integrator_id, lds_st, rstr);
+  return tb(lds_st, p->integrator_id, knx, rstr);
+}
+
+// Resident 256-thread workgroups per CU (= waves per SIMD) of a persistent kernel (left alone if fn is null).
+// The occupancy API over-reports by one for some register counts on ROCm 7.2 (MI355X_MICROARCH.md
+// "Residency"), and a persistent grid with a non-resident workgroup serialises a whole extra round:
+// bound it by the VGPR allocation too.
+static int resident_blocks(StepFn fn, int* out) {
+  if (!fn) return PCG_OK;
+  int nb = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, BLOCK, 0));
+  hipFuncAttributes fa;
+  HIP_TRY(hipFuncGetAttributes(&fa, (const void*)fn));
+  const int alloc = ((fa.numRegs + 7) / 8) * 8;
+  const int by_vgpr = alloc > 0 ? 512 / alloc : 8;
+  nb = std::min(nb, std::min(by_vgpr, 8));
+  *out = nb > 0 ? nb : 1;
+  return PCG_OK;
+}
+
+// The work-queue kernels [per_env_t] of the plan's integrator: the adaptive pairs' own launch, the guarded plans' fix-up
+static const StepFn* queue_table(const Kernels& k, int integ) {
+  switch (integ) {
+    case PCG_INT_DOPRI5: return k.queue;
+    case PCG_INT_RODAS4: return k.queue_r4;
+    case PCG_INT_RODAS5: return k.queue_r5;
+    case PCG_INT_RK4G:
+    case PCG_INT_T5G: return k.queue_fix;
+    default: return nullptr;
+  }
+}
+static const StepFn* queue_w1_table(const Kernels& k, int integ) {
+  return integ == PCG_INT_RODAS5 ? k.queue_r5w1 : k.queue_r4w1;
+}
+
+// Launch geometry of the work-queue kernel [pe] (pcg_step_queue.hpp): resident 256-thread workgroups per CU by the
+// register allocation (= waves per SIMD), the largest tile (<= 1024 slots, four per lane) whose LDS fits that many
+// workgroups in the CU's budget; sb = the schedule bytes its launches stage behind the tile.
+static int queue_geometry(pcg_plan* p, const Kernels& k, int pe, size_t sb) {
+  const StepFn* qtab = queue_table(k, p->integrator_id);
+  if (!qtab || !qtab[pe]) return PCG_OK;
+  const bool ros = is_ros_pair(p->integrator_id);
+  hipFuncAttributes fa;
+  HIP_TRY(hipFuncGetAttributes(&fa, (const void*)qtab[pe]));
+  const int alloc = ((fa.numRegs + 7) / 8) * 8;
+  const int bpc = std::max(1, std::min(4, alloc > 0 ? 512 / alloc : 1));
+  // tile cap: four envs per lane for the explicit pair (tuned in round 2); the Rosenbrock pair's attempts per env are
+  // heavy-tailed (median 17, 1 % above 70, maximum ~100 on BASELINE configs[2]) and want the largest pool
+  const int tcap = ros ? QSORT : QSORT / 2;
+  int best_t = 0, best_b = 1, t1 = 0;
+  for (int b = bpc; b >= 1; --b) {
+    int T = tcap;
+    while (T >= QBLOCK && k.queue_lds(T) + sb > LDS_CU / b) T -= 64;
+    if (T < QBLOCK) continue;
+    if (b == 1) t1 = T;
+    if (b * T > best_b * best_t) {
+      best_t = T;
+      best_b = b;
+    }
+    if (T == tcap && !ros) break;  // the full tile at the highest occupancy that allows it
+  }
+  p->q_tile[pe] = best_t;
+  p->q_bpc[pe] = best_b;
+  p->q_tile1[pe] = t1;
+  if (best_t > 0) {
+    // (the whole CU's LDS: a launch may also park its tile's state there when that fits, see queue_shape)
+    const StepFn wide = p->integrator_id == PCG_INT_DOPRI5 ? k.queue_w[pe] : nullptr;
+    const StepFn fns[3] = {qtab[pe], ros ? queue_w1_table(k, p->integrator_id)[pe] : nullptr, wide};
+    for (StepFn f : fns)
+      if (f) HIP_TRY(hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_CU));
+  }
+  return PCG_OK;
+}
+
+// Every occupancy and work-queue tile the plan could use, from the cfg and the kernel table alone (the PCG_OPT_* options
+// set after creation choose among them): no launch queries the device or changes the plan, so a capture never does.
+// Plans without ahead-of-time kernels (PCG_MODEL_USER) have nothing to settle.
+static int plan_geometry(pcg_plan* p) {
+  if (p->model_id == PCG_MODEL_USER) return PCG_OK;
+  const Kernels& k = kernels(p->kid);
+  const int integ = p->integrator_id, ls = lean_scheme(integ);
+  for (int e = 0; e < 2; ++e) {
+    PCG_TRY(resident_blocks(k.stream[integ][e], &p->stream_occ[e]));
+    if (ls >= 0) {
+      PCG_TRY(resident_blocks(k.pipe[ls][e], &p->pipe_occ[0][e]));
+      PCG_TRY(resident_blocks(k.pipe_ar[ls][e], &p->pipe_occ[1][e]));
+    }
+  }
+  if (integ == PCG_INT_RK4)
+    for (int i = 0; i < k.nfeat; ++i) PCG_TRY(resident_blocks(k.feat[i].fn, &p->feat_occ[i]));
+  // (a per-env-t launch stages the schedules behind the tile where a one-env-per-lane kernel of the plan would)
+  PCG_TRY(queue_geometry(p, k, 0, 0));
+  size_t integ_lds;
+  classic_shape(p, k, false, &integ_lds);
+  return queue_geometry(p, k, 1, sched_in_lds_bytes(p->hc, integ_lds));
+}
+
 int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   if (!out || !cfg) return PCG_E_NULL;
   *out = nullptr;
@@ -825,29 +952,17 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   p->model_id = cfg->model_id;
   p->kid = kernel_id_for(cfg);
   p->integrator_id = cfg->integrator_id;
-  p->lds_stages = 0;
-  p->variant = 0;
-  p->stream_bpc = 0;
   p->nt_stores = 1;  // measured: 20.3 -> 18.7 us per launch on the cstr workload (profiles/)
-  p->num_cus = 0;
-  p->stream_occ[0] = p->stream_occ[1] = 0;
-  p->pipe_occ[0][0] = p->pipe_occ[0][1] = p->pipe_occ[1][0] = p->pipe_occ[1][1] = 0;
-  for (int i = 0; i < MAX_FEAT; ++i) p->feat_occ[i] = 0;
-  p->q_bpc[0] = p->q_bpc[1] = p->q_tile[0] = p->q_tile[1] = p->q_tile1[0] = p->q_tile1[1] = 0;
-  p->env_offset = 0;
-  p->dC = nullptr;
-  p->dsched = nullptr;
-  p->dlean = nullptr;
-  p->jit_fn[0] = p->jit_fn[1] = nullptr;
-  p->jit_integ = p->jit_rhs = p->jit_roll = nullptr;
-  p->nx = cfg->nx;
+  p->no_fixup = std::getenv("PCG_NO_FIXUP") != nullptr;
+  p->no_flat = std::getenv("PCG_NO_FLAT") != nullptr;
+  p->q_force_lean = std::getenv("PCG_Q_FORCE_LEAN") != nullptr;
+  p->nx = cfg->nx;  // (every other field starts zeroed)
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&p->num_cus, hipDeviceAttributeMultiprocessorCount, p->device);
   if (e != hipSuccess) { delete p; return (int)e; }
   const int rows = cfg->nsp + cfg->nd;
   const bool emp = (cfg->flags & PCG_F_UNC_EMPIRICAL) && cfg->nunc > 0;
   const size_t n_emp = emp ? (size_t)cfg->unc_emp_off[cfg->nunc] : 0;
-  p->sched_bytes = sizeof(double) * (size_t)(rows > 0 ? rows : 1) * cfg->N;
   // behind the schedule rows and the sample tables: the per-step table of the lean kernels (LeanStep[N], 128-byte records)
   const size_t lean_off = (((size_t)(rows > 0 ? rows : 1) * cfg->N + n_emp) + 15) & ~(size_t)15;  // in doubles
   const size_t sched_alloc = sizeof(double) * lean_off + sizeof(LeanStep) * (size_t)cfg->N;
@@ -867,18 +982,14 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   if (e == hipSuccess && n_emp)  // empirical sample tables behind the schedule rows
     e = hipMemcpy(p->dsched + (size_t)rows * cfg->N, cfg->unc_emp, sizeof(double) * n_emp, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (p->dC) (void)hipFree(p->dC);
-    if (p->dsched) (void)hipFree(p->dsched);
-    delete p;
+    (void)pcg_plan_destroy(p);
     return (int)e;
   }
   if (cfg->user_cons_src || cfg->user_reward_src || cfg->user_rhs_src) {
     JitModule jm;
     rc = jit_kernels(cfg, p->kid, p->device, &jm);
     if (rc != PCG_OK) {
-      (void)hipFree(p->dC);
-      (void)hipFree(p->dsched);
-      delete p;
+      (void)pcg_plan_destroy(p);
       return rc;
     }
     p->jit_fn[0] = jm.fn[0];
@@ -889,23 +1000,26 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
     // Rosenbrock pairs keep nx^2 doubles per lane in LDS: past 48 KB per workgroup (nx >= 10) a kernel has to be told.
     // Decided HERE, so that a plan that cannot run says so at creation and not at its first step.
     const int jnx = cfg->model_id == PCG_MODEL_USER ? cfg->nx : kernels(p->kid).nx;
-    const size_t need = sizeof(double) * integ_lds_doubles(jnx, cfg->integrator_id, false) +
-                        sizeof(double) * (size_t)(p->hc.nsp + p->hc.nd) * p->hc.N;
+    const size_t need = sizeof(double) * integ_lds_doubles(jnx, cfg->integrator_id, false) + sched_bytes(p->hc);
     if (need > 48 * 1024) {
       hipFunction_t fns[3] = {jm.fn[0], jm.fn[1], jm.integ};
       for (hipFunction_t f : fns) {
         if (!f) continue;
         const hipError_t ae = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)(need < 160 * 1024 ? need : 160 * 1024));
+                                                  (int)std::min(need, LDS_MAX));
         if (ae != hipSuccess) {
           (void)hipGetLastError();
-          (void)hipFree(p->dC);
-          (void)hipFree(p->dsched);
-          delete p;
+          (void)pcg_plan_destroy(p);
           return PCG_E_UNSUPPORTED;
         }
       }
     }
+  }
+  rc = plan_geometry(p);
+  if (rc != PCG_OK) {
+    (void)hipGetLastError();
+    (void)pcg_plan_destroy(p);
+    return rc;
   }
   *out = p;
   return PCG_OK;
@@ -981,431 +1095,312 @@ static int fill_args(const pcg_plan* p, const pcg_buffers* io, StepArgs* a) {
 
 static inline unsigned grid_for(int64_t B, int block = BLOCK) { return (unsigned)((B + block - 1) / block); }
 
-// Resident 256-thread workgroups per CU (= waves per SIMD) of a persistent kernel; < 0: -(hipError_t).
-// The occupancy API over-reports by one for some register counts on ROCm 7.2 (MI355X_MICROARCH.md
-// "Residency"), and a persistent grid with a non-resident workgroup serialises a whole extra round:
-// bound it by the VGPR allocation too.
-static int resident_blocks(StepFn fn) {
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, BLOCK, 0);
-  if (e != hipSuccess) return -(int)e;
-  hipFuncAttributes fa;
-  e = hipFuncGetAttributes(&fa, (const void*)fn);
-  if (e != hipSuccess) return -(int)e;
-  const int alloc = ((fa.numRegs + 7) / 8) * 8;
-  const int by_vgpr = alloc > 0 ? 512 / alloc : 8;
-  if (nb > by_vgpr) nb = by_vgpr;
-  if (nb > 8) nb = 8;
-  return nb > 0 ? nb : 1;
+// anything the lean kernels compile out: observation noise, Gaussian or per-env disturbances, a_delta, the terminal "batch"
+// reward, the tracking reward, constraints
+static bool has_extras(const DevConst& c, const pcg_buffers* io) {
+  return (c.flags & (PCG_F_NOISE | PCG_F_GAUSS_DIST | PCG_F_A_DELTA | PCG_F_REWARD_BATCH | PCG_F_REWARD_TRACK)) || c.ncon > 0 ||
+         io->d != nullptr;
 }
 
-// Launch geometry of the DOPRI5 work-queue kernel (pcg_step_queue.hpp): resident 256-thread workgroups per CU by the
-// register allocation (= waves per SIMD), the largest tile (<= 1024 slots, four per lane) whose LDS fits that many
-// workgroups in 160 KB.
-static int queue_geometry(pcg_plan* p, const Kernels& k, int pe, size_t sched_bytes) {
-  if (p->q_tile[pe] != 0) return PCG_OK;
-  hipFuncAttributes fa;
-  const bool guarded = p->integrator_id == PCG_INT_RK4G || p->integrator_id == PCG_INT_T5G;  // their fix-up launch
+// A route that took the launch: its status
+static bool taken(int* rc, int status) {
+  *rc = status;
+  return true;
+}
+
+// Rodas4, launches of at most ~one full tile per CU (measured: 1024 envs per CU 0.361 -> 0.337 ms; 1366 per CU no
+// difference; 4096 per CU 1.47 -> 1.71 ms): ONE workgroup per CU on the instantiation that keeps the whole loop in
+// registers, every wave alone on its SIMD
+// (the fifth-order pair spills more at two waves per SIMD -- 480 B of scratch per lane against 352 -- and takes the shape up to
+// the 1366 envs per CU of BASELINE configs[4]'s segment, whose lean tile of 1408 slots still fits the CU's LDS with its
+// state: 330 against 337 us per step, HBM traffic 1.06 x the algorithmic bytes against 1.9 x; under the fourth-order pair
+// the same shape was 12 % SLOWER than two workgroups per CU, profiles/r5/mixed_lean_layout.txt, mixed_rodas5.txt)
+static bool queue_one_per_cu(const pcg_plan* p, const Kernels& k, int64_t B, int pe) {
+  const int w1_cap = p->integrator_id == PCG_INT_RODAS5 ? 1500 : 1200;  // envs per CU up to which the shape is taken
+  return is_ros_pair(p->integrator_id) && queue_w1_table(k, p->integrator_id)[pe] && p->q_tile1[pe] >= QBLOCK &&
+         B <= (int64_t)p->num_cus * w1_cap && B > (int64_t)p->num_cus * QBLOCK;
+}
+
+// The explicit pair at two waves per SIMD: ONE 512-thread workgroup per CU on a tile of up to 2048 slots instead of two
+// 256-thread workgroups on 1024 each.  The lanes and the envs per lane are the same, the pool is twice as deep, and the
+// two waves of a SIMD drain the same queue: with two workgroups a wave whose SIMD-mate's tile ran dry early finished
+// alone (per-wave stamps, tools/queue_probe.py: the 10-state cascade's waves ended between 424 and 737 us of a 737 us
+// launch).  Taken when every workgroup still gets >= 1.75 envs per lane.
+// (The Rosenbrock pair in this shape -- one 512-thread workgroup per CU, both waves of a SIMD on one tile of 1024 -- was
+// built and measured in round 5: a wave that shares its SIMD takes 6.8 us per attempt, i.e. 3.4 us per wave-attempt
+// against 3.5 alone; 320-323 us per launch against 305-326: declined, profiles/r5/r4wide_sweep.txt.)
+static bool queue_wide(const pcg_plan* p, const Kernels& k, int64_t B, int pe, bool fixup) {
+  return !is_ros_pair(p->integrator_id) && !fixup && k.queue_w[pe] && B >= (int64_t)p->num_cus * (7 * 2 * QBLOCK / 4);
+}
+
+// The shape of one work-queue launch (pcg_step_queue.hpp) from the plan's settled geometry: no HIP calls.
+// sb: the schedule bytes the launch stages behind the tile; forced: at any tile fill (fix-up launches are).
+struct QueueShape {
+  StepFn fn;       // null: not taken (the tiles would be too thin)
+  unsigned grid;   // workgroups of `block` threads, `lds` bytes of dynamic LDS each
+  int block;
+  size_t lds;
+  int32_t q_tile;  // slots | QT_* flags
+};
+static int queue_shape(const pcg_plan* p, const Kernels& k, int64_t B, int pe, size_t sb, bool fixup, bool forced,
+                       QueueShape* s) {
+  s->fn = nullptr;
+  if (p->q_tile[pe] <= 0) return PCG_OK;
   const bool ros = is_ros_pair(p->integrator_id);
-  const StepFn* q_w1 = p->integrator_id == PCG_INT_RODAS5 ? k.queue_r5w1 : k.queue_r4w1;
-  const StepFn qfn = (p->integrator_id == PCG_INT_RODAS5 ? k.queue_r5 : ros ? k.queue_r4 : guarded ? k.queue_fix : k.queue)[pe];
-  hipError_t e = hipFuncGetAttributes(&fa, (const void*)qfn);
-  if (e != hipSuccess) return (int)e;
-  const int alloc = ((fa.numRegs + 7) / 8) * 8;
-  int bpc = alloc > 0 ? 512 / alloc : 1;
-  bpc = bpc < 1 ? 1 : (bpc > 4 ? 4 : bpc);
-  if (const char* ev = std::getenv("PCG_Q_BPC")) {  // measurement switch: fewer resident workgroups per CU
-    const int v = std::atoi(ev);
-    if (v >= 1 && v < bpc) bpc = v;
+  const bool w1 = queue_one_per_cu(p, k, B, pe), wide = queue_wide(p, k, B, pe, fixup);
+  const int qb = wide ? 2 * QBLOCK : QBLOCK, bpc = (w1 || wide) ? 1 : p->q_bpc[pe];
+  const size_t lds_wg = LDS_CU / bpc;
+  int T = w1 ? p->q_tile1[pe] : p->q_tile[pe];
+  if (wide) {
+    T = QSORT;
+    while (T >= qb && k.queue_lds(T) + sb > LDS_CU) T -= 64;
   }
-  const size_t lds_cu = 160 * 1024 - 2048;
-  // tile cap: four envs per lane for the explicit pair (tuned in round 2); the Rosenbrock pair's attempts per env are
-  // heavy-tailed (median 17, 1 % above 70, maximum ~100 on BASELINE configs[2]) and want the largest pool
-  const int tcap = ros ? QSORT : QSORT / 2;
-  int best_t = 0, best_b = 1, t1 = 0;
-  for (int b = bpc; b >= 1; --b) {
-    int T = tcap;
-    while (T >= QBLOCK && k.queue_lds(T) + sched_bytes > lds_cu / b) T -= 64;
-    if (T < QBLOCK) continue;
-    if (b == 1) t1 = T;
-    if (b * T > best_b * best_t) {
-      best_t = T;
-      best_b = b;
-    }
-    if (T == tcap && !ros) break;  // the full tile at the highest occupancy that allows it
+  const int64_t nwg = std::min((int64_t)p->num_cus * bpc, (B + qb - 1) / qb);  // no workgroup with less than one env per lane
+  s->grid = (unsigned)nwg; s->block = qb;
+  if (fixup) {  // a tile is a compact list of up to T MARKED envs (+ 4 bytes per slot: which env), the state stays in the batch
+    T = p->q_tile[pe];
+    while (T > qb && k.queue_lds(T) + 4 * (size_t)T + 8 + sb > lds_wg) T -= 64;
+    if (T < qb) return PCG_E_UNSUPPORTED;  // (the scan of the fix-up kernel parks QB envs per round: a smaller tile never advances)
+    s->fn = k.queue_fix[pe];
+    s->lds = k.queue_lds(T) + 4 * (size_t)T + 8 + sb;
+    s->q_tile = T;
+    return PCG_OK;
   }
-  p->q_tile[pe] = best_t > 0 ? best_t : -1;
-  p->q_bpc[pe] = best_b;
-  p->q_tile1[pe] = t1;
-  if (best_t > 0) {
-    // (the whole CU's LDS: a launch may also park its tile's state there when that fits, see step_impl)
-    e = hipFuncSetAttribute((const void*)qfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cu);
-    if (e != hipSuccess) return (int)e;
-    if (ros && q_w1[pe]) {
-      e = hipFuncSetAttribute((const void*)q_w1[pe], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cu);
-      if (e != hipSuccess) return (int)e;
-    }
-    if (p->integrator_id == PCG_INT_DOPRI5 && k.queue_w[pe]) {
-      e = hipFuncSetAttribute((const void*)k.queue_w[pe], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cu);
-      if (e != hipSuccess) return (int)e;
-    }
+  // The queue only pays when its tiles are well filled: with fewer than ~1.75 envs per lane in a sub-tile the
+  // re-balancing gain (measured 1.11x at 2.0 on BASELINE configs[2]) no longer covers the bookkeeping (0.99x at
+  // 1.33: the ME segment of configs[4]) -- such launches stay on the classic kernel.
+  const int64_t per = (B + nwg - 1) / nwg, nsub = (per + T - 1) / T, sub = (per + nsub - 1) / nsub;
+  if (sub < (7 * qb) / 4 && !forced) return PCG_OK;
+  auto fit = [qb](int64_t n) { return std::max(qb, (int)((n + 63) / 64 * 64)); };  // slots for n envs
+  // LDS for the sub-tile this launch actually walks, not for the largest one the plan could (the kernel derives the
+  // same number of sub-tiles from the smaller stride); the tile's state goes to LDS too when that still leaves room
+  // for the other workgroups of the CU
+  T = std::min(T, fit(sub));
+  // A workgroup that has its CU to itself and whose tile's state does not fit in LDS walks two half tiles that do, as
+  // long as a lane still gets two envs (the 20-state cascade at B = 2^18: 1024 envs per CU, 2 x 512 with 80 KB of state
+  // each).  Scattered 8-byte accesses of a state that stays in the batch reach HBM as 32-byte sectors -- a tile's rows
+  // do not survive in L2 between a lane's pick-up and its neighbours' -- 592 MB per launch against 114 MB of algorithm;
+  // from LDS the launch moves 137 MB (1.21 x) and takes 1.7 % longer (two envs per lane instead of four for the
+  // longest-first order; profiles/r4/queue_probe/).
+  // (a full tile whose state fits in the LEAN layout -- below -- is preferred to two half tiles)
+  const int nu = p->hc.na + p->hc.nd;
+  const bool lean_fits = k.queue_lds_x_lean && k.queue_lds_x_lean(T, nu) + sb <= lds_wg;
+  if (!lean_fits && bpc == 1 && !wide && k.queue_lds_x(T) + sb > LDS_CU) {
+    const int64_t sub2 = (per + 2 * nsub - 1) / (2 * nsub);
+    if (sub2 >= 2 * qb && k.queue_lds_x(fit(sub2)) + sb <= LDS_CU) T = fit(sub2);
   }
+  // waves of a workgroup that take part in the cooperative phase of a Rodas4 tile (pcg_step_queue.hpp): the heavy envs of
+  // a tile are few (1-2 % at the default threshold) and a wave carries eight at a time -- ONE wave with its groups busy
+  // where the workgroup has the CU to itself, two where two workgroups share it (me10_ros4 at B = 2^18: all four waves
+  // 326.8 us, two 312.9, one 311.6 at threshold 58; profiles/r5/coop_sweep.txt)
+  int32_t flags = ros ? (w1 ? 1 : 2) << QT_COOPW_SHIFT : 0;
+  s->lds = k.queue_lds(T) + sb;
+  if (!p->q_force_lean && k.queue_lds_x(T) + sb <= lds_wg) {
+    flags |= QT_XLDS;
+    s->lds = k.queue_lds_x(T) + sb;
+  } else if (lean_fits && k.queue_lds_x_lean(T, nu) + sb <= lds_wg) {  // (T may have changed)
+    // the LEAN tile layout (pcg_step_queue.hpp, QTile; round 5) where it is what lets the state in: no first-step and
+    // step-count arrays, only the configured disturbance values of the held input.  configs[4]'s extraction segment
+    // (349,524 envs = 683 per workgroup, two workgroups per CU: 98.8 KB each in the full layout, 76.2 in this one) moved
+    // 5.1 x its algorithmic bytes with its state in the batch (profiles/r5/pmc.json)
+    flags |= QT_XLDS | QT_LEAN;
+    s->lds = k.queue_lds_x_lean(T, nu) + sb;
+  }
+  s->fn = w1 ? queue_w1_table(k, p->integrator_id)[pe] : wide ? k.queue_w[pe] : queue_table(k, p->integrator_id)[pe];
+  s->q_tile = T | flags;
   return PCG_OK;
 }
 
-// Fill every lazily queried occupancy of the plan's candidate persistent kernels (done before a stream
-// capture so that no query runs while capturing).
-static int warm_occupancy(pcg_plan* p) {
-  const Kernels& k = kernels(p->kid);
-  for (int e = 0; e < 2; ++e) {
-    const int ls = lean_scheme(p->integrator_id);
-    if (ls >= 0 && k.pipe[ls][e] && p->pipe_occ[0][e] == 0) {
-      const int q = resident_blocks(k.pipe[ls][e]);
-      if (q < 0) return -q;
-      p->pipe_occ[0][e] = q;
-    }
-    if (k.stream[p->integrator_id][e] && p->stream_occ[e] == 0) {
-      const int q = resident_blocks(k.stream[p->integrator_id][e]);
-      if (q < 0) return -q;
-      p->stream_occ[e] = q;
-    }
-  }
-  if ((p->integrator_id == PCG_INT_DOPRI5 && k.queue[0]) || ((p->integrator_id == PCG_INT_RK4G || p->integrator_id == PCG_INT_T5G) && k.queue_fix[0]) ||
-      (is_ros_pair(p->integrator_id) && k.queue_r4[0])) {
-    const int rc = queue_geometry(p, k, 0, 0);
-    if (rc != PCG_OK) return rc;
-  }
-  if (p->integrator_id == PCG_INT_RK4)
-    for (int i = 0; i < k.nfeat; ++i)
-      if (p->feat_occ[i] == 0) {
-        const int q = resident_blocks(k.feat[i].fn);
-        if (q < 0) return -q;
-        p->feat_occ[i] = q;
-      }
-  return PCG_OK;
+// A work-queue launch: the adaptive plans' own (a.fixup = 0), or the second launch of a guarded plan (a.fixup = 1)
+static bool launch_queue(const pcg_plan* p, const Kernels& k, StepArgs a, int pe, bool forced, hipStream_t st, int* rc) {
+  QueueShape q;
+  const int status = queue_shape(p, k, a.B, pe, a.sched_in_lds ? sched_bytes(p->hc) : 0, a.fixup, forced, &q);
+  if (status != PCG_OK) return taken(rc, status);
+  if (!q.fn) return false;
+  const bool ros = is_ros_pair(p->integrator_id);
+  a.q_tile = q.q_tile;
+  // (Rodas4: the fit of MEImpl::cost_key_ros) sort-key weight 0 / 10 / 20 / 33 -> me10 0.689 / 0.684 / 0.683 / 0.719 ms,
+  // configs[4] shard 0.964 / 0.938 / 0.920 / 0.924 ms (profiles/r2/queue_w_sweep.txt)
+  a.q_w = ros ? 3.56f : 20.0f;
+  // Rodas4 with two workgroups per CU: a wave that carries one of the 128 heaviest envs of its tile raises its issue
+  // priority (s_setprio) -- it then runs at the speed of a wave that has its SIMD to itself (2.9 instead of 4.7 us per
+  // attempt) while its SIMD-mate fills the gaps; the two workgroups of a CU start their heaviest envs on different
+  // SIMDs.  configs[4]'s ME segment (349,524 envs: too many for one tile per CU): 484 -> 430 us; no effect on the
+  // explicit pair (profiles/r3/queue_prio_sweep.txt).
+  a.q_prio = ros ? 128 : 0;
+  hipLaunchKernelGGL(cov(q.fn), dim3(q.grid), dim3(q.block), q.lds, st, a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// ---- pcg_step: the routes, tried in this order by step_impl; each says whether it took the launch (*rc: its status) ----
+struct StepCall {
+  const pcg_plan* p;
+  const Kernels& k;
+  const pcg_buffers* io;
+  StepArgs a;
+  int pe;                 // per-env step counters (io->t): 1
+  bool lds_st, extras, auto_reset;
+  int block;              // workgroup and dynamic LDS of the one-env-per-lane kernels
+  size_t shmem;
+  hipStream_t st;
+};
+
+// run-time compiled general kernel with the plan's user expressions
+static bool step_jit(StepCall& s, int* rc) {
+  if (!s.p->jit_fn[0]) return false;
+  if (s.lds_st) return taken(rc, PCG_E_UNSUPPORTED);
+  void* argv[1] = {&s.a};
+  return taken(rc, (int)hipModuleLaunchKernel(cov_jit(s.p->jit_fn[s.pe]), grid_for(s.io->B, s.block), 1, 1, s.block, 1, 1,
+                                              (unsigned)s.shmem, s.st, argv, nullptr));
+}
+
+// per-env uncertain parameters: dedicated general kernel
+static bool step_unc(StepCall& s, int* rc) {
+  if (s.p->hc.nunc <= 0) return false;
+  if (!s.io->p_unc) return taken(rc, PCG_E_NULL);
+  const StepFn fn = s.k.step_unc[s.p->integrator_id][s.pe];
+  if (!fn) return taken(rc, PCG_E_UNSUPPORTED);
+  const size_t sh = s.pe ? sched_in_lds_bytes(s.p->hc, 0) : 0;
+  if (sh) s.a.sched_in_lds = 1;
+  const int ub = tb(false, s.p->integrator_id);
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(s.io->B, ub)), dim3(ub), sh, s.st, s.a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// Adaptive plans: the work-queue kernel (lanes that finish early pull the next env from an LDS tile).
+// PCG_OPT_VARIANT 1 keeps the classic one-env-per-lane kernel (A/B measurement), PCG_OPT_LDS_STAGES too;
+// PCG_OPT_VARIANT 5 takes the queue for any model and any tile fill.
+static bool step_queue(StepCall& s, int* rc) {
+  const int integ = s.p->integrator_id;
+  const bool forced = s.p->variant == 5;
+  if ((integ != PCG_INT_DOPRI5 && !is_ros_pair(integ)) || s.lds_st || (s.p->variant != 0 && !forced) ||
+      !queue_table(s.k, integ)[s.pe] || !(s.k.queue_default || forced))
+    return false;
+  return launch_queue(s.p, s.k, s.a, s.pe, forced, s.st, rc);
+}
+
+// streaming (persistent, prefetching, 16 B/lane) kernel for the lean lock-stepped path
+// Adaptive stepping is left to the one-wave-per-workgroup classic kernel unless a streaming variant is forced:
+// lanes take different numbers of steps, and a persistent grid fixes each wave's share of the batch up front,
+// whereas the dispatcher hands single-wave workgroups to whichever SIMD slot frees first.
+static bool step_lean(StepCall& s, int* rc) {
+  const pcg_plan* p = s.p; const Kernels& k = s.k; const pcg_buffers* io = s.io;
+  const int integ = p->integrator_id, v = p->variant;
+  const int ls = lean_scheme(integ);  // fixed-step schemes with a lean pipelined kernel (RK4, CV8)
+  const StepFn* const pipe = ls >= 0 ? k.pipe[ls] : nullptr;
+  const bool pipe_ok = (v == 0 || v == 4 || v == 5) && pipe && pipe[0];
+  const bool stream_ok = ls >= 0 || v == 2 || v == 3;
+  // (the lean kernels index envs and row offsets in 32 bits: B < 2^28; larger batches take the classic kernel)
+  if (s.pe || s.extras || s.lds_st || io->viol || (io->status && !pipe_ok) || v == 1 || !stream_ok ||
+      (s.auto_reset && !pipe_ok) || io->B >= ((int64_t)1 << 28) || !(k.stream[integ][0] || pipe_ok))
+    return false;
+  const bool epl2_ok = (k.stream[integ][1] || (pipe_ok && pipe[1])) && (io->B % 2 == 0) && al16(io->x) && al16(io->a) &&
+                       al16(io->obs) && al16(io->rew) && al2(io->done);
+  if (v == 3 && !epl2_ok) return taken(rc, PCG_E_UNSUPPORTED);
+  const int e = (v != 2 && epl2_ok) ? 1 : 0;  // envs per lane - 1
+  // auto (0): the software-pipelined kernel where it exists (measured best on the cstr workload:
+  // 14.9 us vs 15.0 two-sub-tile streaming vs 16.9 plain streaming vs 21 classic, profiles/r1)
+  const bool piped = pipe_ok && pipe[e];
+  const StepFn fn = piped ? (s.auto_reset ? k.pipe_ar[ls][e] : pipe[e]) : k.stream[integ][e];
+  if (!fn) return taken(rc, PCG_E_UNSUPPORTED);  // (a forced streaming variant of a scheme that only has the pipelined kernel)
+  const int occ = piped ? p->pipe_occ[s.auto_reset ? 1 : 0][e] : p->stream_occ[e];
+  int bpc = occ;
+  // HBM-bound lean kernels: five resident workgroups per CU.  More waves per SIMD only lengthen every wave's integration
+  // phase (they share the vector unit round-robin), so the grid's stores leave later and in a shorter burst -- measured on
+  // the cstr headline, interleaved runs of one box (profiles/r4/headline_bisect.txt): 4 / 5 / 6 / 8 per CU = 13.96 /
+  // 12.60 / 13.58 / 15.1 us.  PCG_OPT_STREAM_BLOCKS_PER_CU overrides.
+  if (piped && bpc > 5) bpc = 5;
+  if (p->stream_bpc > 0 && p->stream_bpc <= occ) bpc = p->stream_bpc;
+  const int64_t grid = std::min((int64_t)p->num_cus * bpc, (io->B + BLOCK * (e + 1) - 1) / (BLOCK * (e + 1)));
+  s.a.nt_stores = p->nt_stores;
+  hipLaunchKernelGGL(cov(fn), dim3((unsigned)grid), dim3(BLOCK), 0, s.st, s.a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// Feature-masked pipelined kernel (pcg_step_feat.hpp): RK4 plans of the small models with anything beyond the
+// lean step switched on.  Needs two envs per lane (even B, 16-byte rows); the smallest instantiation whose mask
+// covers what this launch uses is taken.  PCG_OPT_VARIANT 1 forces the classic one-env-per-lane kernel (A/B).
+static bool step_feat(StepCall& s, int* rc) {
+  const pcg_plan* p = s.p; const Kernels& k = s.k; const pcg_buffers* io = s.io;
+  const DevConst& c = p->hc;
+  if (p->integrator_id != PCG_INT_RK4 || k.nfeat == 0 || s.lds_st || !(p->variant == 0 || p->variant == 4 || p->variant == 5))
+    return false;
+  // observation noise, per-env step counters, per-env / Gaussian disturbances: the classic kernel is the faster one
+  // (measured), and a lock-stepped same-launch reset needs every env to end together
+  if (s.pe || io->d || (c.flags & PCG_F_NOISE) || ((c.flags & PCG_F_GAUSS_DIST) && c.nd > 0) ||
+      (s.auto_reset && (c.flags & PCG_F_DONE_ON_CONS) && c.ncon > 0) || (io->B % 2 != 0) || !al16(io->x) || !al16(io->a) ||
+      !al16(io->obs) || !al16(io->rew) || !al2(io->done) || !al2(io->viol) || !al2(io->status) || !al16(io->a_save) ||
+      !al16(io->u_prev) || !al16(io->g) || !al16(io->g_pre))
+    return false;
+  unsigned need = 0;
+  if (c.ncon > 0) need |= FT_CONS;
+  if (c.flags & PCG_F_A_DELTA) need |= FT_ADELTA;
+  if (c.flags & PCG_F_REWARD_TRACK) need |= FT_TRACK;
+  if (c.flags & PCG_F_REWARD_BATCH) need |= FT_BATCH;
+  if (s.auto_reset) need |= FT_AR;
+  int best = -1;
+  for (int i = 0; i < k.nfeat; ++i)
+    if ((k.feat[i].mask & need) == need &&
+        (best < 0 || __builtin_popcount(k.feat[i].mask) < __builtin_popcount(k.feat[best].mask)))
+      best = i;
+  if (best < 0) return false;
+  int bpc = p->feat_occ[best];
+  if (p->stream_bpc > 0 && p->stream_bpc < bpc) bpc = p->stream_bpc;
+  const int64_t grid = std::min((int64_t)p->num_cus * bpc, (io->B + 2 * BLOCK - 1) / (2 * BLOCK));
+  s.a.nt_stores = p->nt_stores;
+  hipLaunchKernelGGL(cov(k.feat[best].fn), dim3((unsigned)grid), dim3(BLOCK), 0, s.st, s.a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// The classic one-env-per-lane kernel, which takes every launch the routes above leave.
+// Guarded plans (PCG_INT_RK4G / PCG_INT_T5G) in TWO launches: the general kernel takes the guarded fixed step of every
+// env and only MARKS the ones it does not trust (done[e] = 2, nothing else of their step stored); the work-queue kernel
+// of the adaptive pair then integrates exactly the marked envs -- longest first, lanes pulling the next one -- and
+// finishes their step.  In one launch the fallback ran inside the wave that met it: with a third of a batch igniting
+// every wave waited for its slowest lane (607 us per 2^20-env step on the full x0 box of the cstr against 362 us for the
+// adaptive pair through the queue alone).  Same arithmetic per env either way (tests: the oracle's t5g / rk4g twins).
+// Costs the calm closed loop one nearly empty launch.  Not with a_delta (env_pre accumulates into a_save: not idempotent).
+static int step_classic(StepCall& s) {
+  const pcg_plan* p = s.p;
+  const int integ = p->integrator_id;
+  s.a.fixup = (integ == PCG_INT_RK4G || integ == PCG_INT_T5G) && !s.lds_st && p->variant == 0 && !(p->hc.flags & PCG_F_A_DELTA) &&
+              s.io->B >= (int64_t)p->num_cus * QBLOCK && !p->no_fixup && p->q_tile[s.pe] > 0;
+  const StepFn fn = s.k.step[integ][s.pe][s.lds_st ? 1 : 0][s.extras ? 1 : 0];
+  if (!fn) return PCG_E_UNSUPPORTED;
+  if (s.shmem > 48 * 1024)  // (depends on PCG_OPT_LDS_STAGES: set at launch)
+    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shmem));
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(s.io->B, s.block)), dim3(s.block), s.shmem, s.st, s.a);
+  int rc = (int)hipGetLastError();
+  if (rc != PCG_OK || !s.a.fixup) return rc;
+  if (!launch_queue(p, s.k, s.a, s.pe, true, s.st, &rc)) return PCG_E_UNSUPPORTED;  // (not reachable: forced)
+  return rc;
 }
 
 static int step_impl(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, void* stream, bool auto_reset,
                      uint64_t reset_seed) {
   StepArgs a;
   int rc = fill_args(p, io, &a);
-  a.auto_reset = auto_reset ? 1 : 0;
-  a.reset_seed = reset_seed;
   if (rc != PCG_OK) return rc;
   if (io->B == 0) return PCG_OK;  // empty batch: nothing to do (zero-size buffers may be NULL)
   if (!io->x || !io->a || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
   const DevConst& c = p->hc;
   if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
   if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
-  a.t_scalar = t;
-  a.seed = seed;
   const bool per_env_t = io->t != nullptr;
   if (!per_env_t && t < 0) return PCG_E_VALUE;  // the lock-stepped counter indexes the schedules (t past N-1 clamps, t < 0 cannot)
+  a.t_scalar = t; a.seed = seed;
+  a.auto_reset = auto_reset ? 1 : 0; a.reset_seed = reset_seed;
   const Kernels& k = kernels(p->kid);
-  const bool lds_st = p->lds_stages && p->integrator_id == PCG_INT_DOPRI5 && k.has_lds_stages;
-  const int knx = p->model_id == PCG_MODEL_USER ? p->nx : k.nx;  // the kernels' compile-time state count
-  const bool rstr = p->model_id != PCG_MODEL_USER && k.ros_structured;  // Rodas4 with the model's own W: no LDS
-  const int block = tb(lds_st, p->integrator_id, knx, rstr);
-  size_t shmem = sizeof(double) * integ_lds_doubles(knx, p->integrator_id, lds_st, rstr);
-  const size_t integ_shmem = shmem;
+  const bool lds_st = lds_stages_on(p, k);
+  StepCall s{p, k, io, a, per_env_t ? 1 : 0, lds_st, has_extras(c, io), auto_reset, 0, 0, (hipStream_t)stream};
+  s.block = classic_shape(p, k, lds_st, &s.shmem);
   if (per_env_t) {
-    const size_t sb = sizeof(double) * (size_t)(c.nsp + c.nd) * c.N;
-    if (sb > 0 && shmem + sb <= (shmem > 48 * 1024 ? 160 : 64) * 1024) {
-      a.sched_in_lds = 1;
-      shmem += sb;
-    }
+    const size_t sb = sched_in_lds_bytes(c, s.shmem);
+    s.a.sched_in_lds = sb > 0;
+    s.shmem += sb;
   }
-  if (p->jit_fn[0]) {  // run-time compiled general kernel with the plan's user expressions
-    if (lds_st) return PCG_E_UNSUPPORTED;
-    void* argv[1] = {&a};
-    const size_t sh = (per_env_t && a.sched_in_lds) ? shmem : integ_shmem;
-    return (int)hipModuleLaunchKernel(cov_jit(p->jit_fn[per_env_t ? 1 : 0]), grid_for(io->B, block), 1, 1, block, 1, 1, (unsigned)sh,
-                                      (hipStream_t)stream, argv, nullptr);
-  }
-  if (c.nunc > 0) {  // per-env uncertain parameters: dedicated general kernel
-    if (!io->p_unc) return PCG_E_NULL;
-    StepFn ufn = k.step_unc[p->integrator_id][per_env_t ? 1 : 0];
-    if (!ufn) return PCG_E_UNSUPPORTED;
-    size_t sh = 0;
-    if (per_env_t) {
-      const size_t sb = sizeof(double) * (size_t)(c.nsp + c.nd) * c.N;
-      if (sb > 0 && sb <= 64 * 1024) {
-        a.sched_in_lds = 1;
-        sh = sb;
-      }
-    }
-    const int ub = tb(false, p->integrator_id);
-    hipLaunchKernelGGL(cov(ufn), dim3(grid_for(io->B, ub)), dim3(ub), sh, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-  }
-  // Adaptive plans: the work-queue kernel (lanes that finish early pull the next env from an LDS tile).
-  // PCG_OPT_VARIANT 1 keeps the classic one-env-per-lane kernel (A/B measurement), PCG_OPT_LDS_STAGES too.
-  const bool r4q = is_ros_pair(p->integrator_id);  // either Rosenbrock pair
-  const StepFn* qtab = p->integrator_id == PCG_INT_RODAS5 ? k.queue_r5 : r4q ? k.queue_r4 : k.queue;
-  const StepFn* q_w1 = p->integrator_id == PCG_INT_RODAS5 ? k.queue_r5w1 : k.queue_r4w1;
-  const bool q_forced = p->variant == 5 || std::getenv("PCG_Q_FORCE") != nullptr;  // PCG_OPT_VARIANT 5: any model
-  // the launch of a work-queue kernel (geometry, tile, LDS): true = taken, rc_out is the launch's status
-  auto queue_launch = [&](StepArgs a, const StepFn* qtab, bool r4q, bool q_forced, int& rc_out) -> bool {
-    const int pe = per_env_t ? 1 : 0;
-    const size_t sb = (per_env_t && a.sched_in_lds) ? sizeof(double) * (size_t)(c.nsp + c.nd) * c.N : 0;
-    rc = queue_geometry(p, k, pe, sb);
-    if (rc != PCG_OK) {
-      rc_out = rc;
-      return true;
-    }
-    if (p->q_tile[pe] > 0) {
-      a.q_tile = p->q_tile[pe];
-      if (const char* ev = std::getenv("PCG_Q_TILE")) {  // measurement switch: smaller tile (A/B)
-        const int tv = std::atoi(ev);
-        if (tv >= QBLOCK && tv <= a.q_tile) a.q_tile = tv;
-      }
-      if (std::getenv("PCG_Q_NOSORT")) a.q_tile |= 0x10000;  // measurement switch: FIFO order
-      if (const char* ev = std::getenv("PCG_Q_REFILL")) a.q_tile |= (std::atoi(ev) & 0x7F) << 20;  // measurement switch
-
-      a.q_w = r4q ? 3.56f : 20.0f;  // (Rodas4: the fit of MEImpl::cost_key_ros) tools/queue_w_sweep.sh: 0 / 10 / 20 / 33 -> me10 0.689 / 0.684 / 0.683 / 0.719 ms, configs[4] shard 0.964 / 0.938 / 0.920 / 0.924 ms
-      if (const char* ev = std::getenv("PCG_Q_W")) a.q_w = (float)std::atof(ev);  // measurement switch: key weight
-      // Rodas4 with two workgroups per CU: a wave that carries one of the 128 heaviest envs of its tile raises its issue
-      // priority (s_setprio) -- it then runs at the speed of a wave that has its SIMD to itself (2.9 instead of 4.7 us per
-      // attempt) while its SIMD-mate fills the gaps; the two workgroups of a CU start their heaviest envs on different
-      // SIMDs.  configs[4]'s ME segment (349,524 envs: too many for one tile per CU): 484 -> 430 us; no effect on the
-      // explicit pair (profiles/r3/queue_prio_sweep.txt).
-      a.q_prio = r4q ? 128 : 0;
-      if (const char* ev = std::getenv("PCG_Q_PRIO")) a.q_prio = std::atoi(ev);  // measurement switch: issue priority
-      // Rodas4, launches of at most ~one full tile per CU (measured: 1024 envs per CU 0.361 -> 0.337 ms; 1366 per CU no
-      // difference; 4096 per CU 1.47 -> 1.71 ms): ONE workgroup per CU on the instantiation that keeps the whole loop in
-      // registers, every wave alone on its SIMD
-      // (the fifth-order pair spills more at two waves per SIMD -- 480 B of scratch per lane against 352 -- and takes the shape up to
-      // the 1366 envs per CU of BASELINE configs[4]'s segment, whose lean tile of 1408 slots still fits the CU's LDS with its
-      // state: 330 against 337 us per step, HBM traffic 1.06 x the algorithmic bytes against 1.9 x; under the fourth-order pair
-      // the same shape was 12 % SLOWER than two workgroups per CU, profiles/r5/mixed_lean_layout.txt, mixed_rodas5.txt)
-      int w1_cap = p->integrator_id == PCG_INT_RODAS5 ? 1500 : 1200;  // envs per CU up to which the one-workgroup-per-CU shape is taken
-      if (const char* ev = std::getenv("PCG_Q_W1CAP")) w1_cap = std::atoi(ev);  // measurement switch
-      bool w1 = r4q && q_w1[pe] && p->q_tile1[pe] >= QBLOCK && io->B <= (int64_t)p->num_cus * w1_cap &&
-                io->B > (int64_t)p->num_cus * QBLOCK;
-      if (const char* ev = std::getenv("PCG_Q_W1")) w1 = w1 && std::atoi(ev) != 0;  // measurement switch
-      if (w1) a.q_tile = (a.q_tile & ~0xFFFF) | p->q_tile1[pe];
-      // waves of a workgroup that take part in the cooperative phase of a Rodas4 tile (pcg_step_queue.hpp): the heavy envs of
-      // a tile are few (1-2 % at the default threshold) and a wave carries eight at a time -- ONE wave with its groups busy
-      // where the workgroup has the CU to itself, two where two workgroups share it (me10_ros4 at B = 2^18: all four waves
-      // 326.8 us, two 312.9, one 311.6 at threshold 58; profiles/r5/coop_sweep.txt).  PCG_Q_COOPW: measurement switch (0 = all)
-      if (r4q) {
-        int cw = w1 ? 1 : 2;
-        if (const char* ev = std::getenv("PCG_Q_COOPW")) cw = std::atoi(ev);
-        a.q_tile |= (cw & 0xF) << 27;
-      }
-      // The explicit pair at two waves per SIMD: ONE 512-thread workgroup per CU on a tile of up to 2048 slots instead of two
-      // 256-thread workgroups on 1024 each.  The lanes and the envs per lane are the same, the pool is twice as deep, and the
-      // two waves of a SIMD drain the same queue: with two workgroups a wave whose SIMD-mate's tile ran dry early finished
-      // alone (per-wave stamps, tools/queue_probe.py: the 10-state cascade's waves ended between 424 and 737 us of a 737 us
-      // launch).  Taken when every workgroup still gets >= 1.75 envs per lane.
-      bool wide = !r4q && !a.fixup && k.queue_w[pe] && io->B >= (int64_t)p->num_cus * (7 * 2 * QBLOCK / 4);
-      // (The Rosenbrock pair in this shape -- one 512-thread workgroup per CU, both waves of a SIMD on one tile of 1024 -- was
-      // built and measured in round 5: a wave that shares its SIMD takes 6.8 us per attempt, i.e. 3.4 us per wave-attempt
-      // against 3.5 alone; 320-323 us per launch against 305-326: declined, profiles/r5/r4wide_sweep.txt.)
-      if (const char* ev = std::getenv("PCG_Q_WIDE")) wide = wide && std::atoi(ev) != 0;  // measurement switch
-      const int qb = wide ? 2 * QBLOCK : QBLOCK;
-      if (wide) {
-        int Tw = QSORT;
-        while (Tw >= qb && k.queue_lds(Tw) + sb > (size_t)(160 * 1024 - 2048)) Tw -= 64;
-        a.q_tile = (a.q_tile & ~0xFFFF) | Tw;
-      }
-      const int q_bpc = (w1 || wide) ? 1 : p->q_bpc[pe];
-      int64_t nwg = (int64_t)p->num_cus * q_bpc;
-      const int64_t cap = (io->B + qb - 1) / qb;  // no workgroup with less than one env per lane
-      if (nwg > cap) nwg = cap;
-      // The queue only pays when its tiles are well filled: with fewer than ~1.75 envs per lane in a sub-tile the
-      // re-balancing gain (measured 1.11x at 2.0 on BASELINE configs[2]) no longer covers the bookkeeping (0.99x at
-      // 1.33: the ME segment of configs[4]) -- such launches stay on the classic kernel.
-      const int64_t per = (io->B + nwg - 1) / nwg;
-      int Tq = a.q_tile & 0xFFFF;
-      const int64_t nsub = (per + Tq - 1) / Tq;
-      const int64_t sub = (per + nsub - 1) / nsub;
-      const bool filled = sub >= (7 * qb) / 4 || q_forced;
-      if (filled) {
-      // LDS for the sub-tile this launch actually walks, not for the largest one the plan could (the kernel derives the
-      // same number of sub-tiles from the smaller stride); the tile's state goes to LDS too when that still leaves room
-      // for the other workgroups of the CU
-      const int Tfit = (int)((sub + 63) / 64 * 64) < qb ? qb : (int)((sub + 63) / 64 * 64);
-      if (Tfit < Tq && !std::getenv("PCG_Q_TILE")) {
-        Tq = Tfit;
-        a.q_tile = (a.q_tile & ~0xFFFF) | Tq;
-      }
-      // A workgroup that has its CU to itself and whose tile's state does not fit in LDS walks two half tiles that do, as
-      // long as a lane still gets two envs (the 20-state cascade at B = 2^18: 1024 envs per CU, 2 x 512 with 80 KB of state
-      // each).  Scattered 8-byte accesses of a state that stays in the batch reach HBM as 32-byte sectors -- a tile's rows
-      // do not survive in L2 between a lane's pick-up and its neighbours' -- 592 MB per launch against 114 MB of algorithm;
-      // from LDS the launch moves 137 MB (1.21 x) and takes 1.7 % longer (two envs per lane instead of four for the
-      // longest-first order; profiles/r4/queue_probe/).  PCG_Q_NOXLDS=1 keeps the full tile.
-      // (a full tile whose state fits in the LEAN layout -- below -- is preferred to two half tiles)
-      const bool lean_fits = !a.fixup && k.queue_lds_x_lean && !std::getenv("PCG_Q_NOXLDS") && !std::getenv("PCG_Q_NOLEAN") &&
-                             k.queue_lds_x_lean(Tq, c.na + c.nd) + sb <= (size_t)(160 * 1024 - 2048) / q_bpc;
-      if (!lean_fits && q_bpc == 1 && !wide && k.queue_lds_x(Tq) + sb > (size_t)(160 * 1024 - 2048) && !std::getenv("PCG_Q_NOXLDS") &&
-          !std::getenv("PCG_Q_TILE")) {
-        const int64_t sub2 = (per + 2 * nsub - 1) / (2 * nsub);
-        const int T2 = (int)((sub2 + 63) / 64 * 64) < qb ? qb : (int)((sub2 + 63) / 64 * 64);
-        if (sub2 >= 2 * qb && k.queue_lds_x(T2) + sb <= (size_t)(160 * 1024 - 2048)) {
-          Tq = T2;
-          a.q_tile = (a.q_tile & ~0xFFFF) | Tq;
-        }
-      }
-      size_t qsh = k.queue_lds(Tq) + sb;
-      const bool force_lean = std::getenv("PCG_Q_FORCE_LEAN") != nullptr;  // test switch: the lean layout wherever it fits
-      if (!force_lean && k.queue_lds_x(Tq) + sb <= (size_t)(160 * 1024 - 2048) / q_bpc && !std::getenv("PCG_Q_NOXLDS")) {
-        a.q_tile |= 0x20000;
-        qsh = k.queue_lds_x(Tq) + sb;
-      } else if (lean_fits && k.queue_lds_x_lean(Tq, c.na + c.nd) + sb <= (size_t)(160 * 1024 - 2048) / q_bpc) {  // (Tq may have changed)
-        // the LEAN tile layout (pcg_step_queue.hpp, QTile; round 5) where it is what lets the state in: no first-step and
-        // step-count arrays, only the configured disturbance values of the held input.  configs[4]'s extraction segment
-        // (349,524 envs = 683 per workgroup, two workgroups per CU: 98.8 KB each in the full layout, 76.2 in this one) moved
-        // 5.1 x its algorithmic bytes with its state in the batch (profiles/r5/pmc.json)
-        a.q_tile |= 0x20000 | 0x40000;
-        qsh = k.queue_lds_x_lean(Tq, c.na + c.nd) + sb;
-      }
-      if (a.fixup) {  // fix-up launch: a tile is a compact list of up to Tq MARKED envs (+ 4 bytes per slot: which env), the
-        // state stays in the batch
-        Tq = p->q_tile[pe];
-        while (Tq > qb && k.queue_lds(Tq) + 4 * (size_t)Tq + 8 + sb > (size_t)(160 * 1024 - 2048) / q_bpc) Tq -= 64;
-        if (Tq < qb) {  // (the scan of the fix-up kernel parks QB envs per round: a tile smaller than that never advances)
-          rc_out = PCG_E_UNSUPPORTED;
-          return true;
-        }
-        a.q_tile = (a.q_tile & ~(0xFFFF | 0x20000)) | Tq;
-        qsh = k.queue_lds(Tq) + 4 * (size_t)Tq + 8 + sb;
-      }
-      hipLaunchKernelGGL(cov(w1 ? q_w1[pe] : wide ? k.queue_w[pe] : qtab[pe]), dim3((unsigned)nwg), dim3(qb), qsh, (hipStream_t)stream, a);
-      rc_out = (int)hipGetLastError();
-      return true;
-      }
-    }
-      return false;
-  };
-  if ((p->integrator_id == PCG_INT_DOPRI5 || r4q) && !lds_st && (p->variant == 0 || p->variant == 5) && qtab[per_env_t ? 1 : 0] &&
-      (k.queue_default || q_forced)) {
-    int qrc = PCG_OK;
-    if (queue_launch(a, qtab, r4q, q_forced, qrc)) return qrc;
-  }
-  // Guarded plans (PCG_INT_RK4G / PCG_INT_T5G) in TWO launches: the general kernel takes the guarded fixed step of every
-  // env and only MARKS the ones it does not trust (done[e] = 2, nothing else of their step stored); the work-queue kernel
-  // of the adaptive pair then integrates exactly the marked envs -- longest first, lanes pulling the next one -- and
-  // finishes their step.  In one launch the fallback ran inside the wave that met it: with a third of a batch igniting
-  // every wave waited for its slowest lane (607 us per 2^20-env step on the full x0 box of the cstr against 362 us for the
-  // adaptive pair through the queue alone).  Same arithmetic per env either way (tests: the oracle's t5g / rk4g twins).
-  // Costs the calm closed loop one nearly empty launch.  Not with a_delta (env_pre accumulates into a_save: not idempotent).
-  bool fixup = (p->integrator_id == PCG_INT_RK4G || p->integrator_id == PCG_INT_T5G) && !lds_st && p->variant == 0 &&
-               k.queue_fix[per_env_t ? 1 : 0] && !(c.flags & PCG_F_A_DELTA) && io->B >= (int64_t)p->num_cus * QBLOCK &&
-               !std::getenv("PCG_NO_FIXUP");
-  if (fixup) {
-    const size_t sbq = (per_env_t && a.sched_in_lds) ? sizeof(double) * (size_t)(c.nsp + c.nd) * c.N : 0;
-    rc = queue_geometry(p, k, per_env_t ? 1 : 0, sbq);
-    if (rc != PCG_OK) return rc;
-    fixup = p->q_tile[per_env_t ? 1 : 0] > 0;
-  }
-  a.fixup = fixup ? 1 : 0;
-  // lean variant when no noise / Gaussian disturbance / constraint work is configured
-  // (the lean kernels also compile out a_delta, the terminal "batch" reward and per-env disturbances)
-  const bool extras = (c.flags & (PCG_F_NOISE | PCG_F_GAUSS_DIST | PCG_F_A_DELTA | PCG_F_REWARD_BATCH | PCG_F_REWARD_TRACK)) ||
-                      c.ncon > 0 || io->d != nullptr;
-  // streaming (persistent, prefetching, 16 B/lane) kernel for the lean lock-stepped path
-  // Adaptive stepping is left to the one-wave-per-workgroup classic kernel unless a streaming variant is forced:
-  // lanes take different numbers of steps, and a persistent grid fixes each wave's share of the batch up front,
-  // whereas the dispatcher hands single-wave workgroups to whichever SIMD slot frees first.
-  const int ls = lean_scheme(p->integrator_id);  // fixed-step schemes with a lean pipelined kernel (RK4, CV8)
-  const StepFn* const pipe = ls >= 0 ? k.pipe[ls] : nullptr;
-  const bool stream_ok = ls >= 0 || p->variant == 2 || p->variant == 3;
-  const bool lean_ar_ok = !auto_reset || ((p->variant == 4 || p->variant == 0 || p->variant == 5) && pipe && pipe[0]);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-  auto al2 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 1u) == 0; };
-  const bool pipe_ok = (p->variant == 4 || p->variant == 0 || p->variant == 5) && pipe && pipe[0];
-  // (the lean kernels index envs and row offsets in 32 bits: B < 2^28; larger batches take the classic kernel)
-  if (!per_env_t && !extras && !lds_st && !io->viol && (!io->status || pipe_ok) && p->variant != 1 && stream_ok && lean_ar_ok &&
-      io->B < ((int64_t)1 << 28) && (k.stream[p->integrator_id][0] || pipe_ok)) {
-    const bool epl2_ok = (k.stream[p->integrator_id][1] || (pipe_ok && pipe[1])) && (io->B % 2 == 0) && al16(io->x) &&
-                         al16(io->a) && al16(io->obs) && al16(io->rew) && al2(io->done);
-    int epl = (p->variant == 2) ? 1 : (epl2_ok ? 2 : 1);
-    if (p->variant == 3 && !epl2_ok) return PCG_E_UNSUPPORTED;
-    if (const char* ev = std::getenv("PCG_LEAN_EPL"))  // measurement switch: one env per lane
-      if (std::atoi(ev) == 1) epl = 1;
-    StepFn sfn = k.stream[p->integrator_id][epl - 1];
-    // auto (0): the software-pipelined kernel where it exists (measured best on the cstr workload:
-    // 14.9 us vs 15.0 two-sub-tile streaming vs 16.9 plain streaming vs 21 classic, profiles/r1)
-    const bool piped = pipe_ok && pipe[epl - 1];
-    if (piped) sfn = auto_reset ? k.pipe_ar[ls][epl - 1] : pipe[epl - 1];
-    if (!sfn) return PCG_E_UNSUPPORTED;  // (a forced streaming variant of a scheme that only has the pipelined kernel)
-    int& occ = piped ? p->pipe_occ[auto_reset ? 1 : 0][epl - 1] : p->stream_occ[epl - 1];
-    if (occ == 0) {
-      const int q = resident_blocks(sfn);
-      if (q < 0) return -q;
-      occ = q;
-    }
-    const int64_t tile_envs = (int64_t)BLOCK * epl;
-    const int64_t ntile = (io->B + tile_envs - 1) / tile_envs;
-    int bpc = occ;
-    // HBM-bound lean kernels: five resident workgroups per CU.  More waves per SIMD only lengthen every wave's integration
-    // phase (they share the vector unit round-robin), so the grid's stores leave later and in a shorter burst -- measured on
-    // the cstr headline, interleaved runs of one box (profiles/r4/headline_bisect.txt): 4 / 5 / 6 / 8 per CU = 13.96 /
-    // 12.60 / 13.58 / 15.1 us.  PCG_OPT_STREAM_BLOCKS_PER_CU overrides.
-    if (piped && bpc > 5) bpc = 5;
-    if (p->stream_bpc > 0 && p->stream_bpc <= occ) bpc = p->stream_bpc;
-    int64_t grid = (int64_t)p->num_cus * bpc;
-    if (grid > ntile) grid = ntile;
-    a.nt_stores = p->nt_stores;
-    if (piped) {  // issue priority by residency slot (step_kernel_pipe); PCG_LEAN_PRIO: measurement override (hex, 2 bits per slot)
-      static const int prio_env = [] { const char* ev = std::getenv("PCG_LEAN_PRIO"); return ev ? (int)std::strtol(ev, nullptr, 16) : -1; }();
-      a.q_prio = prio_env >= 0 ? prio_env : 0;
-      a.q_tile = p->num_cus;
-    }
-    hipLaunchKernelGGL(cov(sfn), dim3((unsigned)grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-  }
-  // Feature-masked pipelined kernel (pcg_step_feat.hpp): RK4 plans of the small models with anything beyond the
-  // lean step switched on.  Needs two envs per lane (even B, 16-byte rows); the smallest instantiation whose mask
-  // covers what this launch uses is taken.  PCG_OPT_VARIANT 1 forces the classic one-env-per-lane kernel (A/B).
-  if (p->integrator_id == PCG_INT_RK4 && k.nfeat > 0 && !lds_st && (p->variant == 0 || p->variant == 4 || p->variant == 5)) {
-    unsigned need = 0;
-    if (c.ncon > 0) need |= FT_CONS;
-    if (c.flags & PCG_F_A_DELTA) need |= FT_ADELTA;
-    if (c.flags & PCG_F_REWARD_TRACK) need |= FT_TRACK;
-    if (c.flags & PCG_F_REWARD_BATCH) need |= FT_BATCH;
-    if (auto_reset) need |= FT_AR;
-    // observation noise, per-env step counters, per-env / Gaussian disturbances: the classic kernel is the faster one
-    // (measured), and a
-    // lock-stepped same-launch reset needs every env to end together
-    bool ok = !per_env_t && !io->d && !(c.flags & PCG_F_NOISE) && !((c.flags & PCG_F_GAUSS_DIST) && c.nd > 0) &&
-              !(auto_reset && (c.flags & PCG_F_DONE_ON_CONS) && c.ncon > 0) && (io->B % 2 == 0) && al16(io->x) &&
-              al16(io->a) && al16(io->obs) && al16(io->rew) && al2(io->done) && al2(io->viol) && al2(io->status) &&
-              al16(io->a_save) && al16(io->u_prev) && al16(io->g) && al16(io->g_pre);
-    int best = -1;
-    for (int i = 0; ok && i < k.nfeat; ++i)
-      if ((k.feat[i].mask & need) == need &&
-          (best < 0 || __builtin_popcount(k.feat[i].mask) < __builtin_popcount(k.feat[best].mask)))
-        best = i;
-    if (best >= 0) {
-      if (p->feat_occ[best] == 0) {
-        const int q = resident_blocks(k.feat[best].fn);
-        if (q < 0) return -q;
-        p->feat_occ[best] = q;
-      }
-      const int64_t tile_envs = (int64_t)BLOCK * 2;
-      const int64_t ntile = (io->B + tile_envs - 1) / tile_envs;
-      int bpc = p->feat_occ[best];
-      if (p->stream_bpc > 0 && p->stream_bpc < bpc) bpc = p->stream_bpc;
-      int64_t grid = (int64_t)p->num_cus * bpc;
-      if (grid > ntile) grid = ntile;
-      a.nt_stores = p->nt_stores;
-      hipLaunchKernelGGL(cov(k.feat[best].fn), dim3((unsigned)grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
-      return (int)hipGetLastError();
-    }
-  }
-  StepFn fn = k.step[p->integrator_id][per_env_t ? 1 : 0][lds_st ? 1 : 0][extras ? 1 : 0];
-  if (!fn) return PCG_E_UNSUPPORTED;
-  if (shmem > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B, block)), dim3(block), shmem, (hipStream_t)stream, a);
-  rc = (int)hipGetLastError();
-  if (rc != PCG_OK || !fixup) return rc;
-  int qrc = PCG_OK;
-  if (!queue_launch(a, k.queue_fix, false, true, qrc)) return PCG_E_UNSUPPORTED;  // (not reachable: the geometry was checked above)
-  return qrc;
+  if (step_jit(s, &rc) || step_unc(s, &rc) || step_queue(s, &rc) || step_lean(s, &rc) || step_feat(s, &rc)) return rc;
+  return step_classic(s);
 }
 
 int pcg_step(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, void* stream) {
@@ -1415,6 +1410,72 @@ int pcg_step(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, void*
 int pcg_step_autoreset(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, uint64_t reset_seed, void* stream) {
   if (plan_ok(p) && io && p->hc.nunc > 0 && !io->p_unc) return PCG_E_NULL;
   return step_impl(p, io, t, seed, stream, true, reset_seed);
+}
+
+// ---- pcg_rollout: the routes, in the order pcg_rollout_strided tries them ---------------------------------------
+// per-env parameters (sampled by the reset before the episode): the general rollout kernel's UNC form
+static bool rollout_unc(const pcg_plan* p, const StepArgs& a, hipStream_t st, int* rc) {
+  if (p->hc.nunc <= 0) return false;
+  const StepFn fn = kernels(p->kid).rollout_unc[p->integrator_id];
+  if (!fn) return taken(rc, PCG_E_UNSUPPORTED);  // RK4 and the explicit pair only, as for stepping
+  const int ub = tb(false, p->integrator_id);
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(a.B, ub)), dim3(ub), 0, st, a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// run-time compiled rollout kernel with the plan's user expressions (general step, one env per lane)
+static bool rollout_jit(const pcg_plan* p, StepArgs a, hipStream_t st, int* rc) {
+  if (!p->jit_fn[0]) return false;
+  void* argv[1] = {&a};
+  const int jb = tb(false, p->integrator_id);
+  return taken(rc, (int)hipModuleLaunchKernel(cov_jit(p->jit_roll), grid_for(a.B, jb), 1, 1, jb, 1, 1, 0, st, argv, nullptr));
+}
+
+// RK4 lean fused rollout, two envs per lane where the rows stay 16-byte aligned
+static bool rollout_lean(const pcg_plan* p, const Kernels& k, const StepArgs& a, const pcg_buffers* io, hipStream_t st, int* rc) {
+  if (has_extras(p->hc, io) || p->integrator_id != PCG_INT_RK4 || io->viol || p->variant == 1 || !k.roll_lean[0]) return false;
+  const bool even = ((a.a_ss | a.a_cs | a.o_ss | a.o_cs | a.r_ss) & 1) == 0;  // 16-byte rows stay 16-byte aligned
+  const bool e2 = even && k.roll_lean[1] && (io->B % 2 == 0) && al16(io->x) && al16(a.a_seq) && al16(io->obs) && al16(io->rew) &&
+                  (!a.obs_seq || al16(a.obs_seq)) && (!a.rew_seq || al16(a.rew_seq)) && al2(io->done);
+  const int epl = e2 ? 2 : 1;
+  hipLaunchKernelGGL(cov(k.roll_lean[epl - 1]), dim3(grid_for(io->B, BLOCK * epl)), dim3(BLOCK), 0, st, a);
+  return taken(rc, (int)hipGetLastError());
+}
+
+// (re)allocates the plan's flat-rollout work space for B envs and clears its counters on the launch stream
+static int flat_workspace(pcg_plan* p, int64_t B, hipStream_t st) {
+  if (p->flat_cap < B) {
+    if (p->flat_ws) HIP_TRY(hipFree(p->flat_ws));
+    p->flat_ws = nullptr; p->flat_cap = 0;
+    HIP_TRY(hipMalloc((void**)&p->flat_ws, sizeof(int32_t) * (4 + 2 * (size_t)B)));
+    p->flat_cap = B;
+  }
+  HIP_TRY(hipMemsetAsync(p->flat_ws, 0, sizeof(int32_t) * 4, st));
+  return PCG_OK;
+}
+
+// The guarded default plan of a model with a guard (PCG_INT_T5G), batches of at least one wave per SIMD: the barrier-free
+// rollout in two passes (pcg_rollout_flat.hpp).  The first pass is this plan's ordinary fused rollout kernel, told to hand
+// an env over at the first step its guard does not trust; the second carries each handed-over env to the end of the rollout
+// on a lane of its own.  Same bits as T pcg_step launches.  Not with a_delta (env_pre accumulates), not while the stream is
+// being captured into a graph before the work space exists (hipMalloc); PCG_NO_FLAT=1 keeps the single-kernel rollout (A/B).
+static bool rollout_flat(pcg_plan* p, const Kernels& k, StepFn first, StepArgs a, bool lds_st, hipStream_t st, int* rc) {
+  if (p->integrator_id != PCG_INT_T5G || !k.roll_hot || lds_st || p->variant != 0 || (p->hc.flags & PCG_F_A_DELTA) || a.T < 2 ||
+      a.B < (int64_t)p->num_cus * 4 * 64 || a.B >= ((int64_t)1 << 31) || p->no_flat)
+    return false;
+  const int status = flat_workspace(p, a.B, st);
+  if (status != PCG_OK) return taken(rc, status);
+  a.flat_q = p->flat_ws;
+  a.flat_hot = p->flat_ws + 4;
+  a.flat_tstar = p->flat_ws + 4 + p->flat_cap;
+  a.fixup = 1;
+  const int block = tb(false, PCG_INT_T5G);
+  hipLaunchKernelGGL(cov(first), dim3(grid_for(a.B, block)), dim3(block), 0, st, a);
+  if (hipError_t e = hipGetLastError()) return taken(rc, (int)e);
+  const int wps = 3;  // persistent waves per SIMD of the second pass (measured: profiles/r6/flat_rollout.txt)
+  a.q_tile = 2;       // ... and the cadence of its step boundaries (rollout_kernel_hot: `every`)
+  hipLaunchKernelGGL(cov(k.roll_hot), dim3((unsigned)(p->num_cus * wps)), dim3(FLAT_BLOCK), 0, st, a);
+  return taken(rc, (int)hipGetLastError());
 }
 
 int pcg_rollout_strided(pcg_plan* p, const pcg_buffers* io, int32_t t0, int32_t T, const double* a_seq,
@@ -1432,90 +1493,25 @@ int pcg_rollout_strided(pcg_plan* p, const pcg_buffers* io, int32_t t0, int32_t 
   if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
   if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
   if (p->jit_fn[0] && !p->jit_roll) return PCG_E_UNSUPPORTED;
-  if (c.nunc > 0) {  // per-env parameters (sampled by the reset before the episode): the general rollout kernel's UNC form
-    if (!io->p_unc) return PCG_E_NULL;
-    const Kernels& ku = kernels(p->kid);
-    const StepFn ufn = p->jit_fn[0] ? nullptr : ku.rollout_unc[p->integrator_id];
-    if (!ufn) return PCG_E_UNSUPPORTED;  // RK4 and the explicit pair only, as for stepping
-    a.t_scalar = t0;
-    a.seed = seed;
-    a.T = T;
-    a.a_seq = a_seq;
-    a.obs_seq = obs_seq;
-    a.rew_seq = rew_seq;
-    a.a_ss = a_step_stride; a.a_cs = a_comp_stride;
-    a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride;
-    a.r_ss = rew_step_stride;
-    if (a.a_cs < io->B || (obs_seq && a.o_cs < io->B)) return PCG_E_DIM;
-    const int ub = tb(false, p->integrator_id);
-    hipLaunchKernelGGL(cov(ufn), dim3(grid_for(io->B, ub)), dim3(ub), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-  }
-  a.t_scalar = t0;
-  a.seed = seed;
-  a.T = T;
-  a.a_seq = a_seq;
-  a.obs_seq = obs_seq;
-  a.rew_seq = rew_seq;
+  if (c.nunc > 0 && !io->p_unc) return PCG_E_NULL;
+  a.t_scalar = t0; a.seed = seed; a.T = T;
+  a.a_seq = a_seq; a.obs_seq = obs_seq; a.rew_seq = rew_seq;
   a.a_ss = a_step_stride; a.a_cs = a_comp_stride;
   a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride;
   a.r_ss = rew_step_stride;
   if (a.a_cs < io->B || (obs_seq && a.o_cs < io->B)) return PCG_E_DIM;
-  if (p->jit_fn[0]) {  // run-time compiled rollout kernel with the plan's user expressions (general step, one env per lane)
-    void* argv[1] = {&a};
-    const int jb = tb(false, p->integrator_id);
-    return (int)hipModuleLaunchKernel(cov_jit(p->jit_roll), grid_for(io->B, jb), 1, 1, jb, 1, 1, 0, (hipStream_t)stream, argv, nullptr);
-  }
+  const hipStream_t st = (hipStream_t)stream;
   const Kernels& k = kernels(p->kid);
-  const bool lds_st = p->lds_stages && p->integrator_id == PCG_INT_DOPRI5 && k.has_lds_stages;
-  const bool extras = (c.flags & (PCG_F_NOISE | PCG_F_GAUSS_DIST | PCG_F_A_DELTA | PCG_F_REWARD_BATCH | PCG_F_REWARD_TRACK)) ||
-                      c.ncon > 0 || io->d != nullptr;
-  if (!extras && p->integrator_id == PCG_INT_RK4 && !io->viol && p->variant != 1 && k.roll_lean[0]) {
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-    const bool ev = ((a.a_ss | a.a_cs | a.o_ss | a.o_cs | a.r_ss) & 1) == 0;  // 16-byte rows stay 16-byte aligned
-    const bool e2 = ev && k.roll_lean[1] && (io->B % 2 == 0) && al16(io->x) && al16(a_seq) && al16(io->obs) &&
-                    al16(io->rew) && (!obs_seq || al16(obs_seq)) && (!rew_seq || al16(rew_seq)) &&
-                    (reinterpret_cast<uintptr_t>(io->done) & 1u) == 0;
-    const int epl = e2 ? 2 : 1;
-    hipLaunchKernelGGL(cov(k.roll_lean[epl - 1]), dim3(grid_for(io->B, BLOCK * epl)), dim3(BLOCK), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-  }
+  if (rollout_unc(p, a, st, &rc) || rollout_jit(p, a, st, &rc) || rollout_lean(p, k, a, io, st, &rc)) return rc;
+  const bool lds_st = lds_stages_on(p, k);
+  const StepFn fn = k.rollout[p->integrator_id][lds_st ? 1 : 0];
+  if (!fn) return PCG_E_UNSUPPORTED;  // the Rosenbrock integrator steps through pcg_step only
+  if (rollout_flat(p, k, fn, a, lds_st, st, &rc)) return rc;
   const int block = tb(lds_st, p->integrator_id);
   const size_t shmem = lds_st ? sizeof(double) * 6 * (size_t)k.nx * BLOCK_LDS : 0;
-  StepFn fn = k.rollout[p->integrator_id][lds_st ? 1 : 0];
-  if (!fn) return PCG_E_UNSUPPORTED;  // the Rosenbrock integrator steps through pcg_step only
-  // The guarded default plan of a model with a guard (PCG_INT_T5G), batches of at least one wave per SIMD: the barrier-free
-  // rollout in two passes (pcg_rollout_flat.hpp).  The first pass is this plan's ordinary fused rollout kernel, told to hand
-  // an env over at the first step its guard does not trust; the second carries each handed-over env to the end of the rollout
-  // on a lane of its own.  Same bits as T pcg_step launches.  Not with a_delta (env_pre accumulates), not while the stream is
-  // being captured into a graph before the work space exists (hipMalloc); PCG_NO_FLAT=1 keeps the single-kernel rollout (A/B).
-  if (p->integrator_id == PCG_INT_T5G && k.roll_hot && !lds_st && p->variant == 0 && !(c.flags & PCG_F_A_DELTA) && T >= 2 &&
-      io->B >= (int64_t)p->num_cus * 4 * 64 && io->B < ((int64_t)1 << 31) && !std::getenv("PCG_NO_FLAT")) {
-    if (p->flat_cap < io->B) {
-      if (p->flat_ws) HIP_TRY(hipFree(p->flat_ws));
-      p->flat_ws = nullptr;
-      p->flat_cap = 0;
-      HIP_TRY(hipMalloc((void**)&p->flat_ws, sizeof(int32_t) * (4 + 2 * (size_t)io->B)));
-      p->flat_cap = io->B;
-    }
-    HIP_TRY(hipMemsetAsync(p->flat_ws, 0, sizeof(int32_t) * 4, (hipStream_t)stream));
-    a.flat_q = p->flat_ws;
-    a.flat_hot = p->flat_ws + 4;
-    a.flat_tstar = p->flat_ws + 4 + p->flat_cap;
-    a.fixup = 1;
-    hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B, block)), dim3(block), shmem, (hipStream_t)stream, a);
-    rc = (int)hipGetLastError();
-    if (rc != PCG_OK) return rc;
-    int wps = 3;  // persistent waves per SIMD of the second pass (measured: profiles/r6/flat_rollout.txt)
-    if (const char* ev = std::getenv("PCG_FLAT_WPS")) wps = std::max(1, std::min(8, std::atoi(ev)));  // measurement switch
-    a.q_tile = 2;  // ... and the cadence of its step boundaries (rollout_kernel_hot: `every`)
-    if (const char* ev = std::getenv("PCG_FLAT_EVERY")) a.q_tile = std::max(1, std::min(64, std::atoi(ev)));  // measurement switch
-    hipLaunchKernelGGL(cov(k.roll_hot), dim3((unsigned)(p->num_cus * wps)), dim3(FLAT_BLOCK), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-  }
   if (shmem > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B, block)), dim3(block), shmem, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B, block)), dim3(block), shmem, st, a);
   return (int)hipGetLastError();
 }
 
@@ -1562,10 +1558,6 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
   for (int j = 0; j < T; ++j)
     if (!a_steps[j] || (d_steps && !d_steps[j])) return PCG_E_NULL;
   pcg_buffers b = *io;
-  {
-    const int wrc = warm_occupancy(p);  // launch geometry is queried lazily: do it outside the capture
-    if (wrc != PCG_OK) return wrc;
-  }
   hipStream_t cs;
   HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   int rc = PCG_OK;
@@ -1681,9 +1673,9 @@ int pcg_integrate(pcg_plan* p, int64_t B, double* x, const double* u, int32_t* n
   }
   if (p->model_id == PCG_MODEL_USER) return PCG_E_PLAN;
   const Kernels& k = kernels(p->kid);
-  const bool lds_st = p->lds_stages && p->integrator_id == PCG_INT_DOPRI5 && k.has_lds_stages;
-  const int block = tb(lds_st, p->integrator_id, k.nx, k.ros_structured);
-  const size_t shmem = sizeof(double) * integ_lds_doubles(k.nx, p->integrator_id, lds_st, k.ros_structured);
+  const bool lds_st = lds_stages_on(p, k);
+  size_t shmem;
+  const int block = classic_shape(p, k, lds_st, &shmem);
   IntKFn fn = k.integ[p->integrator_id][lds_st ? 1 : 0];
   if (!fn) return PCG_E_UNSUPPORTED;
   if (shmem > 48 * 1024)

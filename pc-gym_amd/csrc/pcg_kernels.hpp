@@ -166,7 +166,7 @@ struct StepArgs {
   int32_t t_scalar;
   int32_t sched_in_lds;  // per-env-t kernels: schedules staged in LDS
   int32_t nt_stores;     // stream kernels: non-temporal stores for obs / reward
-  int32_t q_tile;        // work-queue kernel: slots of the LDS tile (<= 1024) | measurement switches in the high bits
+  int32_t q_tile;        // work-queue kernel: slots of the LDS tile | QT_* flags (below); flat rollout: its step cadence
   int32_t auto_reset;    // per-env-t kernels: reset the envs that finished in this step (pcg_step_autoreset)
   uint64_t reset_seed;   // RNG key of those resets
   // rollout
@@ -187,6 +187,13 @@ struct StepArgs {
   int32_t* flat_hot;     // [B] the envs the first pass handed over (in the order they tripped)
   int32_t* flat_tstar;   // [B] the step at which an env left the first pass
 };
+
+// The q_tile word of a work-queue launch: tile slots in the low bits, then how the tile is laid out in LDS and how many
+// waves of a workgroup take part in the cooperative phase (written by pcg_abi.hip, read by pcg_step_queue.hpp)
+constexpr int32_t QT_SLOTS = 0xFFFF;      // slots of the tile
+constexpr int32_t QT_XLDS = 0x20000;      // the tile's state lives in LDS
+constexpr int32_t QT_LEAN = 0x40000;      // the lean LDS layout (QTile): what lets the state fit
+constexpr int QT_COOPW_SHIFT = 27;        // 4 bits: waves in the cooperative phase of a Rosenbrock tile (0 = all)
 
 // ---------------------------------------------------------------------------
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11).  RNG contract:
@@ -1385,25 +1392,6 @@ __global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) voi
         if (i < na) ad[i] = *row_at<V>(A.a + (size_t)i * Bs, o8);
     }
   };
-  // MEASUREMENT SWITCH (PCG_LEAN_PRIO, off by default): issue priority by residency slot -- q_prio holds 2 bits per slot
-  // (slot = blockIdx / CUs, q_tile = CUs), bit 16 raises the priority only once the inputs have landed and the prefetch is
-  // out.  The idea: the waves of a SIMD receive their inputs within a microsecond of each other, share the vector unit
-  // round-robin and finish together, so the grid's stores leave in one burst at the end (tools/timeline_probe.py); distinct
-  // priorities would let them finish one after the other.  Measured (profiles/r4/headline/s4, s5): set at wave start it
-  // delays the low-priority waves' own loads by up to 7 us (+1.3 us per launch); set late it is inside the noise.  Kept for
-  // the next attempt, costs three scalar instructions when off.
-  int pr = 0;
-  if (A.q_prio != 0 && A.q_tile > 0) {
-    const int slot = (int)(blockIdx.x / (uint32_t)A.q_tile);
-    pr = (A.q_prio >> (2 * (slot < 8 ? slot : 7))) & 3;
-  }
-  const bool pr_late = (A.q_prio & 0x10000) != 0;
-  auto raise = [&]() {
-    if (pr == 3) __builtin_amdgcn_s_setprio(3);
-    else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-    else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-  };
-  if (!pr_late) raise();
 #ifdef PCG_TIMELINE  // measurement build (tools/timeline_probe.py): per-wave stamps of the 100 MHz wall clock into A.g
   int tl_it = 0;
 #define PCG_TL(k)                                                                                              \
@@ -1428,7 +1416,6 @@ __global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) voi
     asm volatile("" ::: "memory");
     if (live_n) load(e1, xn, an);
     asm volatile("" ::: "memory");
-    if (pr_late) raise();
     if (live) {
       Pack<EPL> xs[NX], as[NA];
 #pragma unroll
@@ -1463,7 +1450,6 @@ __global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) voi
         store_lean<M, EPL>(A, c, L, e0, xs, out, nt);
       }
     }
-    if (pr_late) __builtin_amdgcn_s_setprio(0);
     PCG_TL(3);
 #ifdef PCG_TIMELINE
     if (itn >= ntile) {
@@ -1882,7 +1868,7 @@ Kernels make_kernels() {
     // Measured (tools/user_model_probe.py, cstr B = 2^20 at 1e-8: ~4 attempts per env step): 90 us through the queue
     // against 38 us for the classic kernel -- sorting, parking and refilling cost more than a cheap env's whole
     // integration.  The queue is the default only where a model declares a cost key, i.e. where the step count is
-    // large and predictable from the input (the extraction models: 1.12-1.23x); PCG_Q_FORCE routes any model to it.
+    // large and predictable from the input (the extraction models: 1.12-1.23x); PCG_OPT_VARIANT 5 routes any model to it.
     k.queue_default = has_cost_key<M>::value;
     if constexpr (has_guard<M>::value) {
       k.queue_fix[0] = step_kernel_queue<M, false, true, PCG_INT_DOPRI5, 0, QBLOCK, true>;

@@ -697,13 +697,10 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
   static_assert(!M::DYNAMIC, "the work-queue kernel is built for the fixed-size models");
   CDevConst& c = *A.C;
   constexpr int NX = M::NX, NA = M::NA, NDM = M::NDM, NU = NA + NDM;
-  const int T = A.q_tile & 0xFFFF;
+  const int T = A.q_tile & QT_SLOTS;
   constexpr bool fix = FIX;  // fix-up launch of a guarded plan (pcg_abi.hip): only the envs the first launch marked
-  const bool nosort = (A.q_tile & 0x10000) != 0;  // measurement switch (PCG_Q_NOSORT)
-  const int refill_hi = (A.q_tile >> 20) & 0x7F;  // measurement switch (PCG_Q_REFILL); 0 = the default
-  // (the default depends on the tile: see where it is used)
   static_assert(QSORT == (1 << QSLOT_BITS), "slot index field");
-  const bool lean = (A.q_tile & 0x40000) != 0;  // the lean LDS layout (QTile; host: it is what lets the state fit)
+  const bool lean = (A.q_tile & QT_LEAN) != 0;  // the lean LDS layout (QTile; host: it is what lets the state fit)
   const int nus = lean ? NA + c.nd : NU;
   double* us = lds;
   double* hs = us + (size_t)nus * T;           // (not in the lean layout)
@@ -718,7 +715,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
   int32_t* cnext = next + 3;  // ... and the head of their queue
   constexpr bool COOP = is_ros_pair(INTEG) && has_coop<M>::value && !FIX;
   const bool coop = COOP && c.coop_thr > 0.0;
-  const bool xlds = (A.q_tile & 0x20000) != 0;  // the tile's state lives in LDS (host: it fits)
+  const bool xlds = (A.q_tile & QT_XLDS) != 0;  // the tile's state lives in LDS (host: it fits)
   double* xs = reinterpret_cast<double*>(next + 4);  // [NX][T] when xlds (8-byte aligned: every array before it is)
   int32_t* eidx = reinterpret_cast<int32_t*>(xs);  // fix-up launch: env (relative to the workgroup's range) of a compact slot
   double* sched_l = xs + (xlds ? (size_t)NX * T : fix ? (size_t)(T + 1) / 2 : 0);  // per-env-t schedule tables behind the tile
@@ -811,7 +808,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
       else if constexpr (has_cost_key<M>::value)
         key = (float)(M::cost_key(kp, pre.u) * dt) + A.q_w * __builtin_logf(__builtin_fmaxf((float)d1, 1.0f));
       else key = (float)(dt / h);  // generic proxy: steps at the initial step size
-      key = nosort ? 1.0f : __builtin_fmaxf(key, 1e-30f);
+      key = __builtin_fmaxf(key, 1e-30f);
       // positive floats order like their bit patterns; the sign bit is free: heavy envs sort in front of all others
       return ((__float_as_uint(key) >> QSLOT_BITS) << QSLOT_BITS) | (uint32_t)s | (heavy ? 0x80000000u : 0u);
     };
@@ -869,7 +866,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
     // idle lanes that trigger a refill: with at most two envs per lane every lane refills once and waiting for company
     // only idles it (me10: 0.678 ms at 8, 0.656 at 2); with more envs per lane the refill code -- executed by the whole
     // wave -- is worth batching (configs[4] shard: 0.916 ms at 8, 0.929 at 2; profiles/r2/queue_refill_sweep.txt)
-    const int refill = refill_hi ? refill_hi : (n <= 2 * QB ? 2 : QREFILL);
+    const int refill = n <= 2 * QB ? 2 : QREFILL;
     PCG_QS(2);
     const QTile<M> Q{us, lean ? nullptr : hs, accs, lean ? nullptr : rejs, flag, T, lean, c.nd, c.d_slot, c.d_default};
     int nh = 0;
@@ -877,7 +874,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
       nh = *nheavy;  // (uniform; written before the sort's barriers)
       // how many of the workgroup's waves take part (0 = all): with few heavy envs per tile every wave would carry a mostly
       // empty set of groups through the phase -- one wave with all eight groups busy costs the tile less
-      const int coop_waves = (A.q_tile >> 27) & 0xF;
+      const int coop_waves = (A.q_tile >> QT_COOPW_SHIFT) & 0xF;
       if (nh > 0 && (coop_waves == 0 || (tid >> 6) < coop_waves)) {
         if (A.q_prio > 0) __builtin_amdgcn_s_setprio(3);  // the heavy envs are the launch's critical path
         coop_integrate<M, QB>(&kp, xlds ? xs : A.x + base, xlds ? (int64_t)T : B, Q, sortbuf, cnext, nh, dt,

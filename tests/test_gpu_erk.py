@@ -306,7 +306,7 @@ def test_guarded_plans_two_launch_form_is_the_single_launch_bit_for_bit(integrat
     trust, the work-queue kernel of the adaptive pair integrates exactly those (pcg_abi.hip) -- where smaller ones keep the
     fallback inside the first kernel (the form the oracle tests above pin).  The arithmetic of an env is the same either way:
     on the ignition box, with observation noise and a constraint, both forms give the same bits in every output, every step,
-    through episode ends (PCG_NO_FIXUP=1 keeps the single launch at any size)."""
+    through episode ends (a plan created with PCG_NO_FIXUP=1 keeps the single launch at any size)."""
     torch = _torch()
     from pcgym_amd import VecEnv
 
@@ -314,19 +314,19 @@ def test_guarded_plans_two_launch_form_is_the_single_launch_bit_for_bit(integrat
     p.update(x0=np.array([0.85, 330.0, 0.85]), uncertainty_percentages={"x0": [0.15 / 0.85, 20.0 / 330.0]}, integrator=integrator,
              noise=True, noise_percentage=0.002)
     B = (1 << 17) + 777
+    monkeypatch.delenv("PCG_NO_FIXUP", raising=False)
     two = VecEnv(copy.deepcopy(p), n_envs=B, seed=4, **kw)
+    monkeypatch.setenv("PCG_NO_FIXUP", "1")  # read when the plan is created
     one = VecEnv(copy.deepcopy(p), n_envs=B, seed=4, **kw)
+    monkeypatch.delenv("PCG_NO_FIXUP")
     two.reset(), one.reset()
     assert torch.equal(two.x, one.x)
     gen = torch.Generator(device="cuda").manual_seed(3)
     escalated = 0
     for i in range(two.spec.N + 3 if kw else 8):
         a = 2 * torch.rand((two.spec.na, B), generator=gen, device="cuda", dtype=torch.float64) - 1
-        monkeypatch.delenv("PCG_NO_FIXUP", raising=False)
         o2, r2, d2, _, _ = two.step(a)
-        monkeypatch.setenv("PCG_NO_FIXUP", "1")
         o1, r1, d1, _, _ = one.step(a)
-        monkeypatch.delenv("PCG_NO_FIXUP", raising=False)
         escalated += int((two.nsteps.sum(dim=0) > 0).sum())
         for name, u, v in (("x", two.x, one.x), ("obs", o2, o1), ("rew", r2, r1), ("done", d2, d1), ("nsteps", two.nsteps, one.nsteps),
                            ("status", two.status, one.status), ("viol", two.viol, one.viol)):

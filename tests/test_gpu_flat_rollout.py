@@ -42,8 +42,13 @@ def test_flat_rollout_equals_stepping_and_the_oracle(B, extras):
     from pcgym_amd import VecEnv
 
     p = _params(extras)
-    envs = [VecEnv(copy.deepcopy(p), n_envs=B, seed=7) for _ in range(3)]
-    e_flat, e_step, e_one = envs
+    e_flat, e_step = (VecEnv(copy.deepcopy(p), n_envs=B, seed=7) for _ in range(2))
+    os.environ["PCG_NO_FLAT"] = "1"  # read when the plan is created
+    try:
+        e_one = VecEnv(copy.deepcopy(p), n_envs=B, seed=7)
+    finally:
+        del os.environ["PCG_NO_FLAT"]
+    envs = [e_flat, e_step, e_one]
     spec = e_flat.spec
     assert spec.integrator == "tsit5g"
     T = spec.N - 1
@@ -64,12 +69,8 @@ def test_flat_rollout_equals_stepping_and_the_oracle(B, extras):
     torch.cuda.synchronize()
     assert _launched(e_flat._lib, "rollout_kernel_hot"), "the two-pass rollout was not taken"
     # (c) the single-kernel rollout (one env per lane for all T steps, fallback inside the lane)
-    os.environ["PCG_NO_FLAT"] = "1"
-    try:
-        o1, r1 = e_one.rollout(acts, collect_obs=True, collect_rew=True)
-        torch.cuda.synchronize()
-    finally:
-        del os.environ["PCG_NO_FLAT"]
+    o1, r1 = e_one.rollout(acts, collect_obs=True, collect_rew=True)
+    torch.cuda.synchronize()
     for name, got_o, got_r, env in (("flat", oq, rq, e_flat), ("single kernel", o1, r1, e_one)):
         assert torch.equal(env.x, e_step.x), f"{name}: final state differs from stepping"
         assert torch.equal(env.status, e_step.status) and int(env.status.sum().item()) == 0

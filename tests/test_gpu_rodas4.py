@@ -78,13 +78,13 @@ def test_integrate_vs_oracle(fix, model, kw, tol):
     assert np.all(np.abs(got - t) <= 1e-4 * np.abs(t) + 1e-6)  # fourth-order pair at 1e-6: its accuracy class
 
 
-def _step_pair(name, B, seed, monkeypatch, force_queue, **kw):
+def _step_pair(name, B, seed, force_queue, **kw):
     torch = _torch()
     from oracle import oracle as O
     from pcgym_amd import VecEnv
 
     if force_queue:
-        monkeypatch.setenv("PCG_Q_FORCE", "1")
+        kw["variant"] = 5  # the work-queue kernel at any tile fill
     p = copy.deepcopy(SC.scenarios()[name]["env_params"])
     p.update(integrator="rodas4")
     p.update(kw.pop("params", {}))
@@ -98,14 +98,14 @@ def _step_pair(name, B, seed, monkeypatch, force_queue, **kw):
 @pytest.mark.parametrize("name", ["me_canonical", "me_dist_cons"])
 @pytest.mark.parametrize("per_env_t", [False, True])
 @pytest.mark.parametrize("kernel", ["queue", "classic"])
-def test_step_vs_oracle_structured(name, per_env_t, kernel, monkeypatch):
+def test_step_vs_oracle_structured(name, per_env_t, kernel):
     """full step tuples (state, observation, reward, done, status, step counts) of the extraction scenarios, 12 steps
     WITHOUT re-synchronisation, through the work-queue kernel (forced: thin tiles too) and the classic kernel"""
     B = 1500 if kernel == "queue" else 700
     kw = dict(per_env_t=per_env_t)
     if kernel == "classic":
         kw["variant"] = 1
-    torch, env, orc = _step_pair(name, B, 11, monkeypatch, kernel == "queue", **kw)
+    torch, env, orc = _step_pair(name, B, 11, kernel == "queue", **kw)
     rng = np.random.default_rng(3)
     for i in range(12):
         a = rng.uniform(-1, 1, (env.spec.na, B))
@@ -123,16 +123,15 @@ def test_step_vs_oracle_structured(name, per_env_t, kernel, monkeypatch):
     env.close()
 
 
-def test_queue_equals_classic_and_is_order_independent(monkeypatch):
+def test_queue_equals_classic_and_is_order_independent():
     """the work-queue kernel against the classic one (bitwise), and against itself on a permuted batch"""
     torch = _torch()
     from pcgym_amd import VecEnv
 
-    monkeypatch.setenv("PCG_Q_FORCE", "1")
     p = copy.deepcopy(SC.scenarios()["me_canonical"]["env_params"])
     p.update(integrator="rodas4")
     B = 30000
-    q, cl, q2 = VecEnv(p, n_envs=B, seed=1), VecEnv(p, n_envs=B, seed=1, variant=1), VecEnv(p, n_envs=B, seed=1)
+    q, cl, q2 = VecEnv(p, n_envs=B, seed=1, variant=5), VecEnv(p, n_envs=B, seed=1, variant=1), VecEnv(p, n_envs=B, seed=1, variant=5)
     gen = torch.Generator(device="cuda").manual_seed(2)
     for e in (q, cl, q2):
         e.reset()
@@ -152,8 +151,8 @@ def test_queue_equals_classic_and_is_order_independent(monkeypatch):
         e.close()
 
 
-def test_autoreset_in_the_same_launch(monkeypatch):
-    torch, env, orc = _step_pair("me_canonical", 900, 70, monkeypatch, True, auto_reset=True,
+def test_autoreset_in_the_same_launch():
+    torch, env, orc = _step_pair("me_canonical", 900, 70, True, auto_reset=True,
                                  params=dict(N=7, tsim=7.0, SP={"X5": [0.3] * 7}))
     N = env.N
     for i in range(2 * (N - 1) + 2):

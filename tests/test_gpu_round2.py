@@ -429,7 +429,7 @@ def test_two_ranks_step_a_sharded_mixed_batch_equal_to_the_unsharded_run(tmp_pat
 @pytest.mark.parametrize("name,B,kw", [("me_reactive", 3001, {}), ("cstr_canonical", 70000, {}), ("me_canonical", 2500, {}),
                                        ("cstr_cons_done_raw", 1500, dict(per_env_t=True, auto_reset=True)),
                                        ("heat_exchanger_sp", 700, {}), ("cryst_adelta", 900, {})])
-def test_work_queue_kernel_equals_the_classic_adaptive_kernel(name, B, kw, monkeypatch):
+def test_work_queue_kernel_equals_the_classic_adaptive_kernel(name, B, kw):
     """DOPRI5 plans run on the LDS work-queue kernel (pcg_step_queue.hpp: lanes pull the next env of a cost-sorted tile
     when theirs is done); PCG_OPT_VARIANT 1 keeps the classic one-env-per-lane kernel.  Same per-env arithmetic ->
     identical step counts and round-off-level states for the accuracy-limited models; ragged batch sizes exercise
@@ -437,10 +437,10 @@ def test_work_queue_kernel_equals_the_classic_adaptive_kernel(name, B, kw, monke
     torch = _torch()
     from pcgym_amd import VecEnv
 
-    monkeypatch.setenv("PCG_Q_FORCE", "1")  # thinly filled tiles too (the host would route them to the classic kernel)
     p = copy.deepcopy(SC.scenarios()[name]["env_params"])
     p["integrator"] = "dopri5"
-    q = VecEnv(copy.deepcopy(p), n_envs=B, seed=3, **kw)
+    # variant 5: thinly filled tiles too (the host would route them to the classic kernel)
+    q = VecEnv(copy.deepcopy(p), n_envs=B, seed=3, variant=5, **kw)
     cl = VecEnv(copy.deepcopy(p), n_envs=B, seed=3, variant=1, **kw)
     q.reset()
     cl.reset()
@@ -463,16 +463,15 @@ def test_work_queue_kernel_equals_the_classic_adaptive_kernel(name, B, kw, monke
     cl.close()
 
 
-def test_work_queue_results_do_not_depend_on_the_batch_order(monkeypatch):
+def test_work_queue_results_do_not_depend_on_the_batch_order():
     """bitwise lane independence: the same envs in a permuted batch land in other tiles, other sort positions and other
     lanes of the work-queue kernel -- and give the same bits (the chaotic extraction model included)."""
     torch = _torch()
     from pcgym_amd import VecEnv
 
-    monkeypatch.setenv("PCG_Q_FORCE", "1")
     p = copy.deepcopy(SC.scenarios()["me_canonical"]["env_params"])
     B = 40000
-    e1, e2 = VecEnv(p, n_envs=B, seed=1), VecEnv(p, n_envs=B, seed=1)
+    e1, e2 = VecEnv(p, n_envs=B, seed=1, variant=5), VecEnv(p, n_envs=B, seed=1, variant=5)
     e1.reset()
     e2.reset()
     gen = torch.Generator(device="cuda").manual_seed(2)

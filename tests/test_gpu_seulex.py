@@ -60,18 +60,17 @@ def test_integrate_serial_vs_oracle():
 
 @pytest.mark.parametrize("per_env_t", [False, True])
 @pytest.mark.parametrize("frac", [0.08, 0.6])
-def test_cooperative_queue_vs_classic_vs_oracle(per_env_t, frac, monkeypatch):
+def test_cooperative_queue_vs_classic_vs_oracle(per_env_t, frac):
     """the cooperative phase (eight lanes per env) against the classic kernel (one lane, bitwise) and the oracle, 8 steps
     without re-synchronisation; frac = 0.6: far more heavy envs in a tile than its workgroup has groups -- the groups refill"""
     torch = _torch()
     from oracle import oracle as O
     from pcgym_amd import VecEnv
 
-    monkeypatch.setenv("PCG_Q_FORCE", "1")
     p = copy.deepcopy(SC.scenarios()["me_dist_cons"]["env_params"])
     p.update(integrator="rodas4", cooperative={"thr": 48})
     B = 2600
-    q = VecEnv(p, n_envs=B, seed=4, per_env_t=per_env_t)
+    q = VecEnv(p, n_envs=B, seed=4, per_env_t=per_env_t, variant=5)
     cl = VecEnv(p, n_envs=B, seed=4, per_env_t=per_env_t, variant=1)
     orc = O.OracleEnv(q.spec, B, seed=4, per_env_t=per_env_t)
     q.reset(), cl.reset(), orc.reset()
@@ -140,16 +139,17 @@ def test_lean_tile_layout_is_the_full_one_bit_for_bit(integrator, per_env_t, mon
     from oracle import oracle as O
     from pcgym_amd import VecEnv
 
-    monkeypatch.setenv("PCG_Q_FORCE", "1")
     p = copy.deepcopy(SC.scenarios()["me_dist_cons"]["env_params"])
     p.update(integrator=integrator)
     if integrator == "rodas4":
         p.update(cooperative={"thr": 48})
     B = 2100
-    full = VecEnv(p, n_envs=B, seed=6, per_env_t=per_env_t)
+    monkeypatch.delenv("PCG_Q_FORCE_LEAN", raising=False)
+    full = VecEnv(p, n_envs=B, seed=6, per_env_t=per_env_t, variant=5)
     cl = VecEnv(p, n_envs=B, seed=6, per_env_t=per_env_t, variant=1)
-    monkeypatch.setenv("PCG_Q_FORCE_LEAN", "1")
-    lean = VecEnv(p, n_envs=B, seed=6, per_env_t=per_env_t)
+    monkeypatch.setenv("PCG_Q_FORCE_LEAN", "1")  # read when the plan is created
+    lean = VecEnv(p, n_envs=B, seed=6, per_env_t=per_env_t, variant=5)
+    monkeypatch.delenv("PCG_Q_FORCE_LEAN")
     orc = O.OracleEnv(full.spec, B, seed=6, per_env_t=per_env_t)
     for e in (full, cl, lean, orc):
         e.reset()
@@ -159,9 +159,7 @@ def test_lean_tile_layout_is_the_full_one_bit_for_bit(integrator, per_env_t, mon
         if not full.spec.normalise_a:
             a = (a + 1) * (full.spec.a_high - full.spec.a_low)[:, None] / 2 + full.spec.a_low[:, None]
         at = torch.tensor(a, device=full.device)
-        monkeypatch.delenv("PCG_Q_FORCE_LEAN")
         full.step(at), cl.step(at)
-        monkeypatch.setenv("PCG_Q_FORCE_LEAN", "1")
         lean.step(at)
         orc.step(a)
         for other in (full, cl):

@@ -1,11 +1,10 @@
 """Soak of the work-queue kernel against the classic adaptive kernel: random batch sizes (partial tiles, several tiles per
 workgroup, fewer envs than lanes), models, counter modes, auto-reset; states, step counts, outputs must agree (bitwise for
-the extraction model).  PCG_Q_FORCE routes every size to the queue.    python tools/queue_soak.py [iterations]"""
+the extraction model).  PCG_OPT_VARIANT 5 routes every size to the queue.    python tools/queue_soak.py [iterations]"""
 import copy
 import os
 import sys
 
-os.environ["PCG_Q_FORCE"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -37,7 +36,7 @@ def main():
         if ros:
             p.pop("rtol", None), p.pop("atol", None)
         p.pop("noise", None), p.pop("noise_percentage", None)
-        q = VecEnv(copy.deepcopy(p), n_envs=B, seed=it, per_env_t=pe, auto_reset=ar)
+        q = VecEnv(copy.deepcopy(p), n_envs=B, seed=it, per_env_t=pe, auto_reset=ar, variant=5)
         c = VecEnv(copy.deepcopy(p), n_envs=B, seed=it, per_env_t=pe, auto_reset=ar, variant=1)
         q.reset(), c.reset()
         if pe:  # spread the per-env counters so that some envs finish (and reset) inside the window

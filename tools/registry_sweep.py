@@ -1,6 +1,6 @@
 """Default-path cost of the registry models that have a recorded scenario: us per step of B envs at each model's default
 integrator settings, through the default dispatch, the classic one-env-per-lane kernel (PCG_OPT_VARIANT 1) and -- for
-adaptive plans -- the work-queue kernel forced on (PCG_Q_FORCE).  Guards against a routing that is slower than the
+adaptive plans -- the work-queue kernel forced on (PCG_OPT_VARIANT 5).  Guards against a routing that is slower than the
 plain kernel (round 2 found one: cstr DOPRI5 through the queue).
 
     python tools/registry_sweep.py [B]        (needs a GPU)
@@ -34,14 +34,11 @@ def main():
 
         spec = EnvSpec(copy.deepcopy(p))
         steps = min(spec.N - 1, 40)
-        os.environ.pop("PCG_Q_FORCE", None)
         t_def, _ = run(copy.deepcopy(p), B, steps=steps, reps=3)
         t_cls, _ = run(copy.deepcopy(p), B, variant=1, steps=steps, reps=3)
         t_q = float("nan")
         if spec.integrator == "dopri5":
-            os.environ["PCG_Q_FORCE"] = "1"
-            t_q, _ = run(copy.deepcopy(p), B, steps=steps, reps=3)
-            os.environ.pop("PCG_Q_FORCE", None)
+            t_q, _ = run(copy.deepcopy(p), B, variant=5, steps=steps, reps=3)
         flag = "  <-- default slower than classic" if t_def > 1.08 * t_cls else ""
         print("%-22s %-30s %-7s %9.1f | %9.1f | %9.1f%s" % (name, spec.model.name, spec.integrator, t_def, t_cls, t_q, flag))
 

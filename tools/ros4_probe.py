@@ -13,7 +13,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import scenarios as SC  # noqa: E402
 from pcgym_amd import VecEnv  # noqa: E402
 
-os.environ["PCG_Q_FORCE"] = "1"
 integs = sys.argv[1:] or ["rodas4", "dopri5"]
 for integ in integs:
     for B, label in ((1 << 16, "1 env/lane, 256 WG: one wave per SIMD"), (1 << 17, "1 env/lane, 512 WG: two waves per SIMD"),
@@ -21,7 +20,7 @@ for integ in integs:
         for LG in ((5.0, 1000.0), (250.0, 500.0)):
             p = copy.deepcopy(SC.scenarios()["me_canonical"]["env_params"])
             p.update(integrator=integ, N=400, tsim=400.0, SP={"X5": [0.3] * 400})
-            env = VecEnv(p, n_envs=B)
+            env = VecEnv(p, n_envs=B, variant=5)  # the work-queue kernel at any tile fill
             env.reset()
             lo, hi = env.spec.a_low, env.spec.a_high
             an = [2 * (LG[i] - lo[i]) / (hi[i] - lo[i]) - 1 for i in range(2)]
