@@ -105,3 +105,143 @@ def adaptive_check(model_name, x_gpu, x_orc, ns_gpu, ns_orc, tag, tol=1e-11, x_t
         if not same.all():
             assert ex[~same].max() <= max(1e3 * tol, 1e-9), (tag, "envs with another step sequence", ex[~same].max())
     return ex
+
+
+# ---- the sweep configurations (tests/test_gpu_sweeps.py, tests/test_gpu_tile_walks.py) ----------------------------------------
+FIXED = ("rk4", "cv8")
+GUARDED = ("rk4g", "tsit5g")  # models with a guard hook only (pcg_models.hpp: has_guard -- the cstr)
+FULL = ("cstr", "four_tank", "multistage_extraction", "multistage_extraction_reactive", "crystallization",
+        "first_order_system", "hydraulic_tank", "nonsmooth_control")  # Model::FULL: streaming / pipelined / LDS-stage kernels
+
+
+def _models():
+    """first scenario of every registry model (the tools' rule)"""
+    out, seen = [], set()
+    for name, sc in SC.scenarios().items():
+        p0 = sc["env_params"]
+        m = p0.get("model")
+        if m is None or m in seen or p0.get("custom_model") is not None:
+            continue
+        seen.add(m)
+        out.append((m, name))
+    return out
+
+
+MODELS = _models()
+SCEN = dict(MODELS)
+# the extraction models carry two instantiations each: eq_exponent == 2 (the reference's default: multiply-only kernels,
+# PCG_KID_ME_SQ / _REACTIVE_SQ) and the pow() form (Model<PCG_MODEL_ME>, <PCG_MODEL_ME_REACTIVE>): "^1.5" selects the latter
+MODEL_KEYS = [m for m, _ in MODELS] + ["multistage_extraction^1.5", "multistage_extraction_reactive^1.5"]
+
+
+def _registry_object(model, **params):
+    """an object the way the reference's registry classes look to make_env (pcgym.py:150-153): class name, info()"""
+    from pcgym_amd.models import get_model
+
+    mi = get_model(model)
+    info = {"parameters": {**mi.parameters, **params}, "states": list(mi.states), "inputs": list(mi.inputs),
+            "disturbances": list(mi.disturbances)}
+    return type(model, (), {"info": lambda self: info, "int_method": "hip"})()
+
+
+def sweep_params(key, integ, feat="scen", **over):
+    """env_params of the model's first scenario under `integ`, in one of three feature sets:
+      scen  as the scenario has it
+      lean  nothing beyond the set-point reward (the kernels' lean forms: EXTRAS = false, pipelined / streaming paths)
+      cons  lean + one constraint row with the penalty on (EXTRAS = true, the feature-masked kernels of the small models)"""
+    model, _, expo = key.partition("^")
+    p = copy.deepcopy(SC.scenarios()[SCEN[model]]["env_params"])
+    if expo:
+        p["custom_model"] = _registry_object(model, eq_exponent=float(expo))
+    p.update(integrator=integ, rtol=1e-6, atol=1e-8)
+    if integ in FIXED + GUARDED:
+        p.pop("rtol"), p.pop("atol")
+    if integ == "cv8" and model.startswith("multistage"):
+        p["substeps"] = 256  # (the model's default plan is implicit: the order-8 scheme's own default step is unstable here)
+    for k in ("uncertainty_percentages", "uncertainty_bounds", "distribution", "empirical_distribution"):
+        p.pop(k, None)
+    if feat != "scen":
+        for k in ("a_delta", "a_0", "a_space_act", "noise", "noise_percentage", "constraints", "done_on_cons_vio",
+                  "r_penalty", "custom_reward"):
+            p.pop(k, None)
+        if not p.get("SP"):  # terminal-reward scenarios: a set point on the first state instead
+            from pcgym_amd.models import get_model
+
+            mi = get_model(model)
+            nx = len(mi.states)
+            x0 = np.asarray(p["x0"], dtype=float)[:nx]
+            for k in ("reward_states", "maximise_reward"):
+                p.pop(k, None)
+            sp = float(x0[0]) if x0[0] != 0 else 0.5
+            p["SP"] = {mi.states[0]: [sp] * int(p["N"])}
+            p["x0"] = np.concatenate([x0, [sp]])
+            lo, hi = np.asarray(p["o_space"]["low"], dtype=float)[:nx], np.asarray(p["o_space"]["high"], dtype=float)[:nx]
+            p["o_space"] = {"low": np.concatenate([lo, [min(0.0, 2 * sp)]]), "high": np.concatenate([hi, [max(1.0, 2 * sp)]])}
+            p["r_scale"] = {mi.states[0]: 1.0}
+    if feat == "cons":
+        c0 = float(np.asarray(p["x0"], dtype=float)[0])
+        p.update(constraints=lambda x, u, c0=c0: np.array([x[0] - c0]).reshape(-1,), done_on_cons_vio=False, r_penalty=True)
+    p.update(over)
+    return p
+
+
+# VecEnv arguments of a step dispatch:
+#            auto     the library's own choice at this batch size
+#            odd      the same with an odd batch (one env per lane in the lean kernels: EPL = 1)
+#            classic  PCG_OPT_VARIANT 1: the one-env-per-lane general kernels
+#            queue    PCG_OPT_VARIANT 5: the in-workgroup work queue whatever the model and batch (adaptive pairs)
+#            lds      PCG_OPT_LDS_STAGES: DOPRI5 with the stage vectors in LDS (Model::FULL)
+#            stream1/2  PCG_OPT_VARIANT 2 / 3: the persistent streaming kernels, one / two envs per lane (RK4, Model::FULL)
+#            nostatus  the library's own choice for a caller that keeps no per-env status byte (the lean RK4 launches of the
+#                      larger full models then take the streaming kernel)
+DISPATCH = {"auto": {}, "odd": {}, "classic": {"variant": 1}, "queue": {"variant": 5}, "lds": {"lds_stages": True},
+            "stream1": {"variant": 2, "track_status": False}, "stream2": {"variant": 3, "track_status": False},
+            "nostatus": {"track_status": False}}
+
+
+def sweep_actions(spec, rng, B, lo=-1.0):
+    """uniform actions over [lo, 1] of the normalised box (the full box by default), physical when the plan wants them"""
+    a = rng.uniform(lo, 1, (spec.na, B))
+    if not spec.normalise_a:
+        a = (a + 1) * (spec.a_high - spec.a_low)[:, None] / 2 + spec.a_low[:, None]
+    return a
+
+
+def worst_rel(xg, xo):
+    """largest difference over every lane, relative to max(|x|, 1e-6 of the component's range over the batch)"""
+    ok = np.isfinite(xo).all(axis=0)
+    assert np.array_equal(np.isfinite(xg).all(axis=0), ok), "failure pattern differs from the oracle's"
+    if not ok.any():
+        return 0.0
+    xs = np.maximum(np.abs(xo[:, ok]), 1e-6 * np.max(np.abs(xo[:, ok]), axis=1, keepdims=True))
+    xs = np.maximum(xs, 1e-300)
+    return float(np.max(np.abs(xg[:, ok] - xo[:, ok]) / xs))
+
+
+# feature-masked pipelined kernels (pcg_step_feat.hpp: RK4 plans of the two small models):
+# name -> (env_params changes, VecEnv arguments, pass the `viol` buffer although no constraint is configured)
+def feat_sets(model):
+    p0 = SC.scenarios()[SCEN[model]]["env_params"]
+    c0 = float(np.asarray(p0["x0"], dtype=float)[0])
+    cons = dict(constraints=lambda x, u, c0=c0: np.array([x[0] - c0]).reshape(-1,), done_on_cons_vio=False, r_penalty=True)
+    track = dict(custom_reward={"kind": "sp_track", "R": 0.05})
+    return {
+        "viol_only": ({}, {}, True),                    # mask 0: the lean step with the `viol` output
+        "viol_autoreset": ({}, {"auto_reset": True}, True),  # FT_AR
+        "cons": (cons, {}, False),                      # FT_CONS
+        "track": (track, {}, False),                    # FT_TRACK
+        "cons_track": ({**cons, **track}, {}, False),   # FT_CONS | FT_TRACK (the constraint-showcase configuration)
+        "a_delta": ({}, {}, False),                     # FT_ALL (the only mask with FT_ADELTA)
+    }
+
+
+def feat_params(model, fs):
+    """(env_params, VecEnv arguments, pass `viol`) of feature set `fs` (feat_sets) on the lean RK4 plan of `model`"""
+    over, kw, viol = feat_sets(model)[fs]
+    p = sweep_params(model, "rk4", "lean")
+    p.update(over)
+    if fs == "a_delta":
+        a_lo, a_hi = np.asarray(p["a_space"]["low"], dtype=float), np.asarray(p["a_space"]["high"], dtype=float)
+        p.update(a_delta=True, a_0=(a_lo + a_hi) / 2, a_space_act={"low": a_lo, "high": a_hi},
+                 a_space={"low": -(a_hi - a_lo) / 20, "high": (a_hi - a_lo) / 20}, normalise_a=True)
+    return p, dict(kw), viol

@@ -21,109 +21,23 @@ Together with tests/test_zz_kernel_coverage.py (which fails on a shipped kernel 
 launched) this is the guard of integrator.py:90-107 for every model of pcgym.py:128-148.
 """
 import copy
+import os
 
 import numpy as np
 import pytest
 
 import scenarios as SC
+# (the configurations are shared with tests/test_gpu_tile_walks.py)
+from helpers import DISPATCH, FIXED, FULL, GUARDED, MODEL_KEYS, SCEN
+from helpers import feat_params as _feat_params
+from helpers import sweep_actions as _actions
+from helpers import sweep_params as _params
+from helpers import worst_rel as _worst
 
 pytestmark = pytest.mark.gpu
 
 ROS = ("rodas3", "rodas4", "rodas5")
-FIXED = ("rk4", "cv8")
 ADAPT = ("dopri5", "tsit5") + ROS
-GUARDED = ("rk4g", "tsit5g")  # models with a guard hook only (pcg_models.hpp: has_guard -- the cstr)
-FULL = ("cstr", "four_tank", "multistage_extraction", "multistage_extraction_reactive", "crystallization",
-        "first_order_system", "hydraulic_tank", "nonsmooth_control")  # Model::FULL: streaming / pipelined / LDS-stage kernels
-
-
-def _models():
-    """first scenario of every registry model (the tools' rule)"""
-    out, seen = [], set()
-    for name, sc in SC.scenarios().items():
-        p0 = sc["env_params"]
-        m = p0.get("model")
-        if m is None or m in seen or p0.get("custom_model") is not None:
-            continue
-        seen.add(m)
-        out.append((m, name))
-    return out
-
-
-MODELS = _models()
-SCEN = dict(MODELS)
-# the extraction models carry two instantiations each: eq_exponent == 2 (the reference's default: multiply-only kernels,
-# PCG_KID_ME_SQ / _REACTIVE_SQ) and the pow() form (Model<PCG_MODEL_ME>, <PCG_MODEL_ME_REACTIVE>): "^1.5" selects the latter
-MODEL_KEYS = [m for m, _ in MODELS] + ["multistage_extraction^1.5", "multistage_extraction_reactive^1.5"]
-
-
-def _registry_object(model, **params):
-    """an object the way the reference's registry classes look to make_env (pcgym.py:150-153): class name, info()"""
-    from pcgym_amd.models import get_model
-
-    mi = get_model(model)
-    info = {"parameters": {**mi.parameters, **params}, "states": list(mi.states), "inputs": list(mi.inputs),
-            "disturbances": list(mi.disturbances)}
-    return type(model, (), {"info": lambda self: info, "int_method": "hip"})()
-
-
-def _params(key, integ, feat="scen", **over):
-    """env_params of the model's first scenario under `integ`, in one of three feature sets:
-      scen  as the scenario has it
-      lean  nothing beyond the set-point reward (the kernels' lean forms: EXTRAS = false, pipelined / streaming paths)
-      cons  lean + one constraint row with the penalty on (EXTRAS = true, the feature-masked kernels of the small models)"""
-    model, _, expo = key.partition("^")
-    p = copy.deepcopy(SC.scenarios()[SCEN[model]]["env_params"])
-    if expo:
-        p["custom_model"] = _registry_object(model, eq_exponent=float(expo))
-    p.update(integrator=integ, rtol=1e-6, atol=1e-8)
-    if integ in FIXED + GUARDED:
-        p.pop("rtol"), p.pop("atol")
-    if integ == "cv8" and model.startswith("multistage"):
-        p["substeps"] = 256  # (the model's default plan is implicit: the order-8 scheme's own default step is unstable here)
-    for k in ("uncertainty_percentages", "uncertainty_bounds", "distribution", "empirical_distribution"):
-        p.pop(k, None)
-    if feat != "scen":
-        for k in ("a_delta", "a_0", "a_space_act", "noise", "noise_percentage", "constraints", "done_on_cons_vio",
-                  "r_penalty", "custom_reward"):
-            p.pop(k, None)
-        if not p.get("SP"):  # terminal-reward scenarios: a set point on the first state instead
-            from pcgym_amd.models import get_model
-
-            mi = get_model(model)
-            nx = len(mi.states)
-            x0 = np.asarray(p["x0"], dtype=float)[:nx]
-            for k in ("reward_states", "maximise_reward"):
-                p.pop(k, None)
-            sp = float(x0[0]) if x0[0] != 0 else 0.5
-            p["SP"] = {mi.states[0]: [sp] * int(p["N"])}
-            p["x0"] = np.concatenate([x0, [sp]])
-            lo, hi = np.asarray(p["o_space"]["low"], dtype=float)[:nx], np.asarray(p["o_space"]["high"], dtype=float)[:nx]
-            p["o_space"] = {"low": np.concatenate([lo, [min(0.0, 2 * sp)]]), "high": np.concatenate([hi, [max(1.0, 2 * sp)]])}
-            p["r_scale"] = {mi.states[0]: 1.0}
-    if feat == "cons":
-        c0 = float(np.asarray(p["x0"], dtype=float)[0])
-        p.update(constraints=lambda x, u, c0=c0: np.array([x[0] - c0]).reshape(-1,), done_on_cons_vio=False, r_penalty=True)
-    p.update(over)
-    return p
-
-
-def _actions(spec, rng, B):
-    a = rng.uniform(-1, 1, (spec.na, B))
-    if not spec.normalise_a:
-        a = (a + 1) * (spec.a_high - spec.a_low)[:, None] / 2 + spec.a_low[:, None]
-    return a
-
-
-def _worst(xg, xo):
-    """largest difference over every lane, relative to max(|x|, 1e-6 of the component's range over the batch)"""
-    ok = np.isfinite(xo).all(axis=0)
-    assert np.array_equal(np.isfinite(xg).all(axis=0), ok), "failure pattern differs from the oracle's"
-    if not ok.any():
-        return 0.0
-    xs = np.maximum(np.abs(xo[:, ok]), 1e-6 * np.max(np.abs(xo[:, ok]), axis=1, keepdims=True))
-    xs = np.maximum(xs, 1e-300)
-    return float(np.max(np.abs(xg[:, ok] - xo[:, ok]) / xs))
 
 
 def _bars(key, integ):
@@ -153,19 +67,6 @@ def _make(p, B, **kw):
 
 
 # ---- step kernels ---------------------------------------------------------------------------------------------------------
-# dispatch:  auto     the library's own choice at this batch size
-#            odd      the same with an odd batch (one env per lane in the lean kernels: EPL = 1)
-#            classic  PCG_OPT_VARIANT 1: the one-env-per-lane general kernels
-#            queue    PCG_OPT_VARIANT 5: the in-workgroup work queue whatever the model and batch (adaptive pairs)
-#            lds      PCG_OPT_LDS_STAGES: DOPRI5 with the stage vectors in LDS (Model::FULL)
-#            stream1/2  PCG_OPT_VARIANT 2 / 3: the persistent streaming kernels, one / two envs per lane (RK4, Model::FULL)
-#            nostatus  the library's own choice for a caller that keeps no per-env status byte (the lean RK4 launches of the
-#                      larger full models then take the streaming kernel)
-DISPATCH = {"auto": {}, "odd": {}, "classic": {"variant": 1}, "queue": {"variant": 5}, "lds": {"lds_stages": True},
-            "stream1": {"variant": 2, "track_status": False}, "stream2": {"variant": 3, "track_status": False},
-            "nostatus": {"track_status": False}}
-
-
 def _sweep_cases():
     out = []
     for key in MODEL_KEYS:
@@ -508,22 +409,6 @@ def test_uncertainty_sweep(key, integ, pe):
 
 
 # ---- feature-masked pipelined kernels (pcg_step_feat.hpp: RK4 plans of the two small models) -----------------------------------
-# name -> (env_params changes, VecEnv arguments, pass the `viol` buffer although no constraint is configured)
-def _feat_sets(model):
-    p0 = SC.scenarios()[SCEN[model]]["env_params"]
-    c0 = float(np.asarray(p0["x0"], dtype=float)[0])
-    cons = dict(constraints=lambda x, u, c0=c0: np.array([x[0] - c0]).reshape(-1,), done_on_cons_vio=False, r_penalty=True)
-    track = dict(custom_reward={"kind": "sp_track", "R": 0.05})
-    return {
-        "viol_only": ({}, {}, True),                    # mask 0: the lean step with the `viol` output
-        "viol_autoreset": ({}, {"auto_reset": True}, True),  # FT_AR
-        "cons": (cons, {}, False),                      # FT_CONS
-        "track": (track, {}, False),                    # FT_TRACK
-        "cons_track": ({**cons, **track}, {}, False),   # FT_CONS | FT_TRACK (the constraint-showcase configuration)
-        "a_delta": ({}, {}, False),                     # FT_ALL (the only mask with FT_ADELTA)
-    }
-
-
 @pytest.mark.parametrize("fs", ["viol_only", "viol_autoreset", "cons", "track", "cons_track", "a_delta"])
 @pytest.mark.parametrize("model", ["cstr", "four_tank"])
 def test_feature_kernels(model, fs):
@@ -531,13 +416,7 @@ def test_feature_kernels(model, fs):
     from oracle import oracle as O
 
     B = 512
-    over, kw, viol = _feat_sets(model)[fs]
-    p = _params(model, "rk4", "lean")
-    p.update(over)
-    if fs == "a_delta":
-        a_lo, a_hi = np.asarray(p["a_space"]["low"], dtype=float), np.asarray(p["a_space"]["high"], dtype=float)
-        p.update(a_delta=True, a_0=(a_lo + a_hi) / 2, a_space_act={"low": a_lo, "high": a_hi},
-                 a_space={"low": -(a_hi - a_lo) / 20, "high": (a_hi - a_lo) / 20}, normalise_a=True)
+    p, kw, viol = _feat_params(model, fs)
     env = _make(p, B, seed=17, **kw)
     spec = env.spec
     if viol:
@@ -569,7 +448,8 @@ def test_feature_kernels(model, fs):
 def test_queue_shapes(key, integ, B, pe):
     """the extraction cascade at the batch sizes that select: 512-thread workgroups (DOPRI5 from 229,376 envs), ONE
     workgroup per CU on the register-only instantiation (the Rosenbrock pairs between 65,536 and 300,000 envs) and two
-    workgroups per CU beyond -- one env step of the full batch, three windows of it against the oracle"""
+    workgroups per CU beyond -- one env step of the full batch against the oracle, every env: these shapes place the envs
+    into tiles and sub-tiles (queue_shape, pcg_abi.hip), and a window would see a few of several hundred workgroups"""
     import torch
     from oracle import oracle as O
 
@@ -580,18 +460,36 @@ def test_queue_shapes(key, integ, B, pe):
     gen = torch.Generator(device="cuda").manual_seed(3)
     a = 2 * torch.rand((spec.na, B), generator=gen, device="cuda", dtype=torch.float64) - 1
     x0 = env.x.clone()
-    env.step(a)
+    og, rg, dg, _, _ = env.step(a)
     assert int(env.status.sum().item()) == 0
-    W = 192
-    for lo in (0, B // 2 - 77, B - W):
-        orc = O.OracleEnv(spec, W, seed=31, per_env_t=pe, env_offset=lo)
-        orc.reset()
-        assert np.allclose(orc.x, x0[:, lo:lo + W].cpu().numpy(), rtol=1e-14)
-        orc.step(a[:, lo:lo + W].cpu().numpy())
-        bar, seq = _bars(key, integ)
-        assert _worst(env.x[:, lo:lo + W].cpu().numpy(), orc.x) <= (bar if bar > 1e-6 else 1e-7)
-        assert np.mean(np.all(env.nsteps[:, lo:lo + W].cpu().numpy() == orc.nsteps, axis=0)) >= seq
+    orc = O.OracleEnv(spec, B, seed=31, per_env_t=pe, n_threads=_threads())
+    orc.reset()
+    assert np.allclose(orc.x, x0.cpu().numpy(), rtol=1e-14)
+    oc, rc, dc = orc.step(a.cpu().numpy())
+    bar, seq = _bars(key, integ)
+    xbar = bar if bar > 1e-6 else 1e-7
+    assert _worst(env.x.cpu().numpy(), orc.x) <= xbar
+    same = np.all(env.nsteps.cpu().numpy() == orc.nsteps, axis=0)
+    assert np.mean(same) >= seq
+    _assert_outputs_match(og, rg, dg, oc, rc, dc, xbar, same)
     env.close()
+
+
+def _threads():
+    """threads of the oracle: the CPUs this process may use, not the machine's"""
+    return int(os.environ.get("OMP_NUM_THREADS", "1") or 1)
+
+
+def _assert_outputs_match(og, rg, dg, oc, rc, dc, xbar, same):
+    """observations at the bar of the state (they are an affine map of it), done exact, and the rewards of the envs that
+    took the oracle's step sequence (`same`) at test_integrator_sweep's bar -- an env with another sequence is held to the
+    oracle through its state and observation (the pow() form of the extraction cascade may take another sequence on half of
+    the envs, _bars)"""
+    og, rg = og.cpu().numpy().T, rg.cpu().numpy()
+    assert np.isfinite(oc).all() and np.isfinite(rc).all()
+    assert np.allclose(og, oc, rtol=xbar, atol=xbar * max(1.0, float(np.max(np.abs(oc)))))
+    assert np.allclose(rg[same], rc[same], rtol=1e-6, atol=1e-9 * (1 + np.max(np.abs(rc), initial=0)))
+    assert np.array_equal(dg.cpu().numpy().astype(np.uint8), dc)
 
 
 @pytest.mark.parametrize("pe", [False, True], ids=["lockstep", "per_env_t"])
@@ -599,7 +497,7 @@ def test_queue_shapes(key, integ, B, pe):
 def test_guarded_fixup_shapes(integ, pe):
     """the guarded plans of the cstr in their two-launch form (from 65,536 envs: the general kernel marks the envs it does
     not trust, the work-queue kernel of the adaptive pair finishes exactly those) on the full x0 box of SURVEY.md section
-    8(d), a third of which ignites: two env steps of the full batch, windows of it against the oracle"""
+    8(d), a third of which ignites: two env steps of the full batch, every env against the oracle"""
     import torch
     from oracle import oracle as O
 
@@ -610,19 +508,18 @@ def test_guarded_fixup_shapes(integ, pe):
     env = _make(p, B, seed=41, per_env_t=pe)
     spec = env.spec
     env.reset()
+    orc = O.OracleEnv(spec, B, seed=41, per_env_t=pe, n_threads=_threads())
+    orc.reset()
     gen = torch.Generator(device="cuda").manual_seed(5)
-    W = 256
     for _ in range(2):
         a = 2 * torch.rand((spec.na, B), generator=gen, device="cuda", dtype=torch.float64) - 1
         x0 = env.x.clone()
-        env.step(a)
+        og, rg, dg, _, _ = env.step(a)
         assert int(env.status.sum().item()) == 0
         assert float((env.nsteps.sum(dim=0) > 0).double().mean().item()) > 0.05  # the fix-up launch had envs to finish
-        for lo in (0, B // 2 - 77, B - W):
-            orc = O.OracleEnv(spec, W, seed=41, per_env_t=pe, env_offset=lo)
-            orc.reset()
-            orc.x[:] = x0[:, lo:lo + W].cpu().numpy()
-            orc.step(a[:, lo:lo + W].cpu().numpy())
-            assert _worst(env.x[:, lo:lo + W].cpu().numpy(), orc.x) <= 1e-9
-            assert np.array_equal(env.nsteps[:, lo:lo + W].cpu().numpy(), orc.nsteps)
+        orc.x[:] = x0.cpu().numpy()
+        oc, rc, dc = orc.step(a.cpu().numpy())
+        assert _worst(env.x.cpu().numpy(), orc.x) <= 1e-9
+        assert np.array_equal(env.nsteps.cpu().numpy(), orc.nsteps)
+        _assert_outputs_match(og, rg, dg, oc, rc, dc, 1e-9, np.ones(B, dtype=bool))
     env.close()
