@@ -49,7 +49,7 @@ typedef unsigned long uintptr_t;
 extern "C" {
 #endif
 
-#define PCG_ABI_VERSION 14
+#define PCG_ABI_VERSION 15
 
 #ifndef PCG_API
 #define PCG_API __attribute__((visibility("default")))
@@ -471,6 +471,58 @@ PCG_API int pcg_rollout_strided(pcg_plan* plan, const pcg_buffers* io, int32_t t
                                 int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
                                 int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                                 int64_t rew_step_stride, uint64_t seed, void* stream);
+
+/* Closed-loop fused rollout with an on-device policy (ABI 15).  The policy is DECLARATIVE: a small fp64 multi-layer
+ * perceptron, the shape stable-baselines3's MlpPolicy produces (the reference evaluates policy.predict(obs) on the host
+ * between two env.step() calls, policy_evaluation.py:86-128):
+ *     h1 = act(W[0] obs + b[0]);  h2 = act(W[1] h1 + b[1]);  a = out_map(W[n_hidden] h + b[n_hidden])
+ * with 0, 1 or 2 hidden layers; n_hidden == 0 is affine state feedback a = W obs + b. */
+#define PCG_ACT_TANH 0
+#define PCG_ACT_RELU 1
+#define PCG_POL_NONE 0   /* a = the last layer's output                        */
+#define PCG_POL_CLIP 1   /* ... clipped to [out_low, out_high]                 */
+#define PCG_POL_TANH 2   /* ... squashed by tanh                               */
+#define PCG_POL_MAX_WIDTH 64
+typedef struct pcg_policy_cfg {
+  int32_t n_in, n_out;        /* must equal the plan's Nobs and na                                  */
+  int32_t n_hidden;           /* 0, 1 or 2 hidden layers                                            */
+  int32_t width[2];           /* 1..PCG_POL_MAX_WIDTH each (entries past n_hidden are ignored)      */
+  int32_t activation;         /* PCG_ACT_TANH | PCG_ACT_RELU                                        */
+  int32_t out_map;            /* PCG_POL_NONE | PCG_POL_CLIP | PCG_POL_TANH                         */
+  double out_low, out_high;   /* PCG_POL_CLIP: out_low <= out_high                                  */
+  const double* W[3];         /* host, row-major [n_next][n_prev]; layers 0 .. n_hidden             */
+  const double* b[3];         /* host, [n_next]                                                     */
+} pcg_policy_cfg;
+typedef struct pcg_policy pcg_policy; /* opaque, immutable after creation */
+
+/* Host-only validation of a policy configuration (usable without a GPU): the status pcg_policy_create() would return
+ * before it touches the device.  PCG_E_DIM: n_in outside 1..PCG_MAX_NOBS, n_out outside 1..PCG_MAX_NA, n_hidden outside
+ * 0..2, a width outside 1..PCG_POL_MAX_WIDTH; PCG_E_NULL: a missing matrix / bias; PCG_E_VALUE: unknown activation /
+ * output map, out_low > out_high (or not finite) under PCG_POL_CLIP, a weight that is not finite. */
+PCG_API int pcg_policy_validate(const pcg_policy_cfg* cfg);
+/* Copies the weights to the current device (synchronous, a few KB).  A policy belongs to that device. */
+PCG_API int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg);
+PCG_API int pcg_policy_destroy(pcg_policy* policy);
+
+/* T env steps in ONE launch with the state in registers and the policy evaluated in the kernel between two steps:
+ *   - the action of step s is policy(observation the env emitted before step s); for s = 0 that is io->obs as
+ *     pcg_reset or the previous call left it.  The observation is exactly what pcg_step would have written (normalised
+ *     if the plan normalises, with noise if the plan has noise: Philox keyed (seed, env, t) as everywhere);
+ *   - the policy output is what the caller would have put into io->a (policy space, before the action map);
+ *     a_seq_out[s] records it; with record_next_action, row T holds policy(observation after the last step), which is
+ *     not applied (the last column of `u` in the reference's rollout, policy_evaluation.py:123-127) -- a_seq_out then
+ *     has T + 1 rows;
+ *   - a_seq_out, obs_seq, rew_seq may each be NULL; layout, strides and 16-byte rules as in pcg_rollout_strided;
+ *     io->x / obs / rew / done receive the last step, as in pcg_rollout.  io->a is not read.
+ * Lock-stepped plans only (io->t == NULL: PCG_E_UNSUPPORTED otherwise).  PCG_E_DIM when the policy's n_in / n_out are not
+ * the plan's Nobs / na.  PCG_E_UNSUPPORTED, before anything is launched: plans with constraint rows, per-env parameters,
+ * user expressions or PCG_MODEL_USER, any integrator other than PCG_INT_RK4 / PCG_INT_CV8.
+ * The call reads the plan and the policy and writes neither: no lazy allocation, no memset -- safe under stream capture
+ * and from several streams at once (on distinct buffers). */
+PCG_API int pcg_rollout_policy(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* policy, int32_t t0, int32_t T,
+                               double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                               int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                               int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
 
 /* pcg_step followed, in the same launch, by the reset of every env that finished in it (gymnasium "same-step"
  * auto-reset: rew / done / viol are those of the finished step; x, obs, t, a_save and the per-env parameters are

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-PCG_ABI_VERSION = 14
+PCG_ABI_VERSION = 15
 PCG_MAX_NX = 24
 PCG_MAX_NA = 5
 PCG_MAX_NDM = 4
@@ -65,6 +65,13 @@ PCG_F_REWARD_TRACK = 0x1000
 PCG_F_REWARD_CRYST = 0x2000
 PCG_MAX_RBOX = 4
 PCG_MAX_EMP = 65536
+
+PCG_ACT_TANH = 0
+PCG_ACT_RELU = 1
+PCG_POL_NONE = 0
+PCG_POL_CLIP = 1
+PCG_POL_TANH = 2
+PCG_POL_MAX_WIDTH = 64
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -158,6 +165,21 @@ class pcg_buffers(C.Structure):
     ]
 
 
+class pcg_policy_cfg(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_int32),
+        ("n_out", C.c_int32),
+        ("n_hidden", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("activation", C.c_int32),
+        ("out_map", C.c_int32),
+        ("out_low", C.c_double),
+        ("out_high", C.c_double),
+        ("W", _pd * 3),
+        ("b", _pd * 3),
+    ]
+
+
 # every extern "C" symbol the header declares (tests check the .so exports all)
 EXPORTS = [
     "pcg_version",
@@ -177,6 +199,10 @@ EXPORTS = [
     "pcg_integrate",
     "pcg_rollout",
     "pcg_rollout_strided",
+    "pcg_policy_validate",
+    "pcg_policy_create",
+    "pcg_policy_destroy",
+    "pcg_rollout_policy",
     "pcg_step_autoreset",
     "pcg_graph_create",
     "pcg_graph_launch",
@@ -228,6 +254,15 @@ def declare(lib):
     lib.pcg_rollout_strided.restype = C.c_int
     lib.pcg_rollout_strided.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_int32, vp, C.c_int64, C.c_int64,
                                         vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_uint64, vp]
+    lib.pcg_policy_validate.restype = C.c_int
+    lib.pcg_policy_validate.argtypes = [C.POINTER(pcg_policy_cfg)]
+    lib.pcg_policy_create.restype = C.c_int
+    lib.pcg_policy_create.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg)]
+    lib.pcg_policy_destroy.restype = C.c_int
+    lib.pcg_policy_destroy.argtypes = [vp]
+    lib.pcg_rollout_policy.restype = C.c_int
+    lib.pcg_rollout_policy.argtypes = [vp, C.POINTER(pcg_buffers), vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int64,
+                                       vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_uint64, vp]
     lib.pcg_step_autoreset.restype = C.c_int
     lib.pcg_step_autoreset.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_uint64, C.c_uint64, vp]
     lib.pcg_graph_create.restype = C.c_int

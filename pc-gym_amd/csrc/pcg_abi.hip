@@ -1524,6 +1524,142 @@ int pcg_rollout(pcg_plan* p, const pcg_buffers* io, int32_t t0, int32_t T, const
                              B, seed, stream);
 }
 
+// ---- closed-loop fused rollout with an on-device MLP policy (pcg_rollout_policy.hpp) ------------------------------------
+struct pcg_policy {
+  uint32_t magic;
+  int device;
+  int n_in, n_out;
+  PolicyDev* dP;  // header + packed weights, immutable after creation
+};
+static constexpr uint32_t POLICY_MAGIC = 0x50434750u;  // 'PCGP'
+
+// layer l of a validated cfg: (rows, columns)
+static void policy_layer_dims(const pcg_policy_cfg* c, int l, int* rows, int* cols) {
+  *cols = l == 0 ? c->n_in : c->width[l - 1];
+  *rows = l == c->n_hidden ? c->n_out : c->width[l];
+}
+
+int pcg_policy_validate(const pcg_policy_cfg* c) {
+  if (!c) return PCG_E_NULL;
+  if (c->n_in < 1 || c->n_in > PCG_MAX_NOBS || c->n_out < 1 || c->n_out > PCG_MAX_NA) return PCG_E_DIM;
+  if (c->n_hidden < 0 || c->n_hidden > 2) return PCG_E_DIM;
+  for (int l = 0; l < c->n_hidden; ++l)
+    if (c->width[l] < 1 || c->width[l] > PCG_POL_MAX_WIDTH) return PCG_E_DIM;
+  if (c->activation != PCG_ACT_TANH && c->activation != PCG_ACT_RELU) return PCG_E_VALUE;
+  if (c->out_map != PCG_POL_NONE && c->out_map != PCG_POL_CLIP && c->out_map != PCG_POL_TANH) return PCG_E_VALUE;
+  if (c->out_map == PCG_POL_CLIP && !(std::isfinite(c->out_low) && std::isfinite(c->out_high) && c->out_low <= c->out_high))
+    return PCG_E_VALUE;
+  for (int l = 0; l <= c->n_hidden; ++l) {
+    if (!c->W[l] || !c->b[l]) return PCG_E_NULL;
+    int rows, cols;
+    policy_layer_dims(c, l, &rows, &cols);
+    for (int i = 0; i < rows * cols; ++i)
+      if (!std::isfinite(c->W[l][i])) return PCG_E_VALUE;
+    for (int i = 0; i < rows; ++i)
+      if (!std::isfinite(c->b[l][i])) return PCG_E_VALUE;
+  }
+  return PCG_OK;
+}
+
+// The device block of a policy: header, then every layer's matrix and bias padded with zeros to the block sizes the
+// kernel unrolls by (pcg_rollout_policy.hpp) -- rows of a hidden layer to POL_HB (fed by the observation) or POL_SB
+// (streamed), rows of the output layer to PCG_MAX_NA, columns to POL_IB (observation) or POL_HB / POL_SB (hidden units).
+static std::vector<double> pack_policy(const pcg_policy_cfg* c) {
+  static_assert(POL_MAX_W == PCG_POL_MAX_WIDTH && POL_MAX_W % POL_HB == 0 && POL_HB % POL_SB == 0, "policy block sizes");
+  auto up = [](int n, int m) { return (n + m - 1) / m * m; };
+  PolicyDev h;
+  std::memset(&h, 0, sizeof(h));
+  h.n_in = c->n_in; h.n_out = c->n_out; h.n_hidden = c->n_hidden; h.act = c->activation; h.out_map = c->out_map;
+  h.out_lo = c->out_low; h.out_hi = c->out_high;
+  for (int l = 0; l < c->n_hidden; ++l) h.w[l] = c->width[l];
+  std::vector<double> data;
+  for (int l = 0; l <= c->n_hidden; ++l) {
+    int rows, cols;
+    policy_layer_dims(c, l, &rows, &cols);
+    const bool outl = l == c->n_hidden;
+    const int prow = outl ? PCG_MAX_NA : up(rows, l == 0 ? POL_HB : POL_SB);
+    const int pcol = l == 0 ? up(cols, POL_IB) : up(cols, l == 1 ? POL_HB : POL_SB);
+    h.ld[l] = pcol;
+    h.offW[l] = (int32_t)data.size();
+    data.resize(data.size() + (size_t)prow * pcol, 0.0);
+    for (int r = 0; r < rows; ++r)
+      for (int k = 0; k < cols; ++k) data[(size_t)h.offW[l] + (size_t)r * pcol + k] = c->W[l][(size_t)r * cols + k];
+    h.offb[l] = (int32_t)data.size();
+    data.resize(data.size() + (size_t)prow, 0.0);
+    for (int r = 0; r < rows; ++r) data[(size_t)h.offb[l] + r] = c->b[l][r];
+  }
+  // (one scalar load may fetch up to sixteen words: the block ends in slack, so that no fetch ends outside it)
+  std::vector<double> blob(sizeof(PolicyDev) / sizeof(double) + data.size() + 16, 0.0);
+  std::memcpy(blob.data(), &h, sizeof(h));
+  std::memcpy(blob.data() + sizeof(PolicyDev) / sizeof(double), data.data(), sizeof(double) * data.size());
+  return blob;
+}
+
+int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) {
+  if (!out) return PCG_E_NULL;
+  *out = nullptr;
+  PCG_TRY(pcg_policy_validate(cfg));
+  pcg_policy* q = new (std::nothrow) pcg_policy();
+  if (!q) return (int)hipErrorOutOfMemory;
+  q->n_in = cfg->n_in; q->n_out = cfg->n_out;
+  const std::vector<double> blob = pack_policy(cfg);
+  hipError_t e = hipGetDevice(&q->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&q->dP, sizeof(double) * blob.size());
+  if (e == hipSuccess) e = hipMemcpy(q->dP, blob.data(), sizeof(double) * blob.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (q->dP) (void)hipFree(q->dP);
+    delete q;
+    return (int)e;
+  }
+  q->magic = POLICY_MAGIC;
+  *out = q;
+  return PCG_OK;
+}
+
+int pcg_policy_destroy(pcg_policy* q) {
+  if (!q) return PCG_OK;
+  if (q->magic != POLICY_MAGIC) return PCG_E_PLAN;
+  q->magic = 0;
+  const hipError_t e = hipFree(q->dP);
+  delete q;
+  return (int)e;
+}
+
+int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
+                       int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
+                       int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
+                       uint64_t seed, void* stream) {
+  StepArgs a;
+  int rc = fill_args(p, io, &a);
+  if (rc != PCG_OK) return rc;
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  const DevConst& c = p->hc;
+  // what the closed-loop kernel does not carry: per-env counters, constraint rows, per-env parameters, run-time compiled
+  // models / expressions, and every integrator but the two fixed-step schemes
+  const int ls = lean_scheme(p->integrator_id);
+  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
+  const PolFn fn = kernels(p->kid).roll_policy[ls];
+  if (!fn) return PCG_E_UNSUPPORTED;
+  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  if (T < 1 || t0 < 0 || (int64_t)t0 + (int64_t)T > 0x7fffffffLL) return PCG_E_VALUE;
+  if (io->B == 0) return PCG_OK;
+  if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
+  if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
+  if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
+  if ((a_seq_out && a_comp_stride < io->B) || (obs_seq && obs_comp_stride < io->B)) return PCG_E_DIM;
+  a.t_scalar = t0; a.seed = seed; a.T = T;
+  a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
+  a.obs_seq = obs_seq; a.rew_seq = rew_seq;
+  a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride; a.r_ss = rew_step_stride;
+  PolicyArgs pa;
+  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
+  pa.record_next = record_next_action ? 1 : 0;
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, pa);
+  return (int)hipGetLastError();
+}
+
 int pcg_reset(pcg_plan* p, const pcg_buffers* io, const uint8_t* mask, uint64_t seed, void* stream) {
   StepArgs a;
   int rc = fill_args(p, io, &a);

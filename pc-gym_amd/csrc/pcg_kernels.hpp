@@ -18,7 +18,8 @@
 //     unit when the batch is lock-stepped, and are staged in LDS when every env carries
 //     its own step counter (per-lane table lookups after masked auto-reset).
 //   * DOPRI5 stage vectors: VGPRs, or LDS [stage][component][lane] (PCG_OPT_LDS_STAGES).
-//   * no MFMA: there is no dense contraction on this path.
+//   * no MFMA: the env step has no dense contraction; the one dense contraction of a closed loop, the policy of
+//     pcg_rollout_policy.hpp, is small enough for scalar-operand FMAs (measured: DESIGN.md section 3).
 //
 // Reference path restated: make_env.step / reset (src/pcgym/pcgym.py:263-500),
 // integration_engine (src/pcgym/integrator.py:65-107,163-182), model RHS
@@ -1730,6 +1731,9 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 }  // namespace pcg
 #include "pcg_step_queue.hpp"
 #include "pcg_rollout_flat.hpp"
+#ifndef __HIPCC_RTC__  // (ahead-of-time kernels only: a run-time compiled plan has no closed-loop rollout)
+#include "pcg_rollout_policy.hpp"
+#endif
 namespace pcg {
 
 using StepFn = void (*)(const StepArgs);
@@ -1740,6 +1744,7 @@ using StepFn = void (*)(const StepArgs);
 // ---------------------------------------------------------------------------
 using RhsKFn = void (*)(CDevConst*, int64_t, int, const double*, const double*, double*);
 using IntKFn = void (*)(CDevConst*, int64_t, int, double*, const double*, int32_t*);
+using PolFn = void (*)(const StepArgs, const PolicyArgs);
 
 // one instantiation of the feature-masked small-model kernel (pcg_step_feat.hpp): serves every launch whose
 // needs are a subset of `mask`
@@ -1782,6 +1787,7 @@ struct Kernels {
   StepFn rollout[PCG_INT_COUNT][2];  // [integrator][lds_stages]
   StepFn rollout_unc[PCG_INT_COUNT]; // fused rollout with per-env parameters (RK4, DOPRI5; null for affine)
   StepFn roll_hot;                   // second pass of the barrier-free rollout of a PCG_INT_T5G plan (models with a guard)
+  PolFn roll_policy[2];              // closed-loop fused rollout with an on-device MLP policy [lean_scheme(integrator)]
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1841,6 +1847,9 @@ Kernels make_kernels() {
   k.step[PCG_INT_CV8][1][0][0] = k.step[PCG_INT_CV8][1][0][1] = step_kernel<M, PCG_INT_CV8, true, false, true>;
   k.integ[PCG_INT_CV8][0] = k.integ[PCG_INT_CV8][1] = integrate_kernel<M, PCG_INT_CV8, false>;
   k.rollout[PCG_INT_CV8][0] = k.rollout[PCG_INT_CV8][1] = rollout_kernel<M, PCG_INT_CV8, false>;
+  // closed-loop fused rollout (pcg_rollout_policy.hpp): the two fixed-step schemes, beside their open-loop kernels
+  k.roll_policy[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel<M, PCG_INT_RK4>;
+  k.roll_policy[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel<M, PCG_INT_CV8>;
   // Tsit5 (the reference's jax method): general kernel, both counter modes, and the integration hook
   k.step[PCG_INT_TSIT5][0][0][0] = k.step[PCG_INT_TSIT5][0][0][1] = step_kernel<M, PCG_INT_TSIT5, false, false, true>;
   k.step[PCG_INT_TSIT5][1][0][0] = k.step[PCG_INT_TSIT5][1][0][1] = step_kernel<M, PCG_INT_TSIT5, true, false, true>;

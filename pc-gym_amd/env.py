@@ -304,6 +304,32 @@ class VecEnv:
         self.t += T
         return obs_seq, rew_seq
 
+    def rollout_policy(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
+                       record_next_action=False):
+        """Fused CLOSED-loop rollout: T steps in one launch, ``policy`` (an :class:`~pcgym_amd.policy.MLPPolicy`)
+        evaluated in the kernel on the observation the env emitted before each step (``env.obs`` for the first).
+        Returns (a_seq (T [+1], na, B) | None, obs_seq (T, Nobs, B) | None, rew_seq (T, B) | None): the policy outputs
+        as the caller would have passed them to step(); with ``record_next_action`` row T is the policy's proposal for
+        the observation after the last step, not applied.  Plans the kernel does not take (constraints, per-env
+        parameters, user models, integrators other than rk4 / cv8) raise PcgError: loop over step() for those."""
+        torch = _torch()
+        if self.per_env_t:
+            raise ValueError("rollout_policy() is lock-stepped only")
+        s, f64, dev, B = self.spec, torch.float64, self.device, self.B
+        T = int(T)
+        a_seq = torch.empty((T + (1 if record_next_action else 0), s.na, B), dtype=f64, device=dev) if collect_actions else None
+        obs_seq = torch.empty((T, s.nobs, B), dtype=f64, device=dev) if collect_obs else None
+        rew_seq = torch.empty((T, B), dtype=f64, device=dev) if collect_rew else None
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_policy(
+            self._plan, self._bufp, policy.handle(dev), self.t, T,
+            a_seq.data_ptr() if collect_actions else None, s.na * B, B,
+            obs_seq.data_ptr() if collect_obs else None, s.nobs * B, B,
+            rew_seq.data_ptr() if collect_rew else None, B,
+            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_policy")
+        self.t += T
+        return a_seq, obs_seq, rew_seq
+
     def capture_steps(self, actions, disturbances=None, with_reset=False):
         """Record ``len(actions)`` consecutive step() launches (starting at the current ``t``, or at a
         full reset if ``with_reset``) as one HIP graph over this env's buffers.

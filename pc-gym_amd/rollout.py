@@ -14,7 +14,8 @@ every array on the GPU in the reference's axis order:
 
 ``reps`` of the reference (independent repetitions of one env) is the env axis B here.
 Closed loop: ``policy(obs (B, Nobs) tensor) -> (B, na)`` (or ``(na, B)``) tensor, one
-kernel launch per step.  Open loop (``actions`` given, no constraint rows to record): the fused
+kernel launch per step -- or, for a declarative :class:`~pcgym_amd.policy.MLPPolicy` on a plan that qualifies, ONE launch
+for the whole episode with the policy evaluated in the kernel (``pcg_rollout_policy``).  Open loop (``actions`` given, no constraint rows to record): the fused
 ``pcg_rollout_strided`` kernel writes straight into these layouts, state in registers.
 """
 from __future__ import annotations
@@ -24,6 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .policy import fused_policy_ok
 
 
 def _torch():
@@ -56,7 +58,9 @@ def _denorm_(t, hm, dim):
 def collect_rollouts(env, policy=None, actions=None):
     """Roll all B envs of a VecEnv through one episode (N-1 steps) and return the reference-shaped dict.
 
-    policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop), or
+    policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop); an ``MLPPolicy`` is evaluated inside
+              the fused rollout kernel when the plan qualifies (``fused_ok`` below, RK4 / CV8, no per-env parameters, no
+              user model) and like any other callable otherwise, or
     actions : (N, na, B) tensor of policy outputs (open loop; row N-1 is only recorded in ``u``).
 
     Recording is zero-copy: each step's kernel writes its observation / reward rows straight into the trajectory
@@ -104,6 +108,19 @@ def collect_rollouts(env, policy=None, actions=None):
         env.t += N - 1
         u = a if a_hm is None else _denorm_(a.clone(), a_hm, 1)  # never scale the caller's tensor in place
         return {"r": r, "x": _denorm_(x, o_hm, 0), "u": u.permute(1, 0, 2)}
+    if policy is not None and fused_ok and fused_policy_ok(s, policy):
+        # closed loop in one launch: the kernel evaluates the policy between two steps and writes observations, policy
+        # outputs (column N-1: the action proposed for the final observation) and rewards in the reference's axis order
+        x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
+        u = torch.empty((s.na, N, B), dtype=f64, device=dev)
+        x[:, 0] = env.obs_soa
+        env._buf.d = None
+        rc = env._lib.pcg_rollout_policy(
+            env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
+            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_policy")
+        env.t += N - 1
+        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
     # per-step path: step-major storage, the env's kernels write into it
     xs = torch.empty((N, s.nobs, B), dtype=f64, device=dev)
     us = torch.empty((N, s.na, B), dtype=f64, device=dev)

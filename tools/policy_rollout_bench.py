@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Closed-loop rollout with an MLP policy: the fused call (pcg_rollout_policy: the policy evaluated in the rollout kernel)
+against the per-step route (collect_rollouts with the same policy as a torch callable: one pcg_step launch and one torch
+evaluation per step, obs and a through HBM) -- the reference's policy_eval.rollout loop, policy_evaluation.py:71-130.
+
+    python tools/policy_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--out FILE]
+
+Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s), both routes through collect_rollouts, so
+both produce the reference's x (Nx, N, B) / u (na, N, B) / r (1, N, B) arrays.  The two routes alternate inside one
+process (`reps` pairs after one warm-up pair each); times are device-event times of whole episodes, the figure compared is
+the median.  The 2 x 64 policy is also reported as a share of the fp64 vector peak (FMAs of the policy alone).
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden")]
+
+SHAPES = {"affine": (), "1x16": (16,), "2x64": (64, 64)}
+FP64_VECTOR_PEAK = 78.6e12  # MI355X, FLOP/s (spec: half the fp32 vector rate)
+
+
+def make_policy(spec, hidden, seed=17):
+    """fixed-seed weights on the normalised observation / action boxes: unsaturated units, outputs mostly inside [-1, 1]"""
+    from pcgym_amd import MLPPolicy
+
+    rng = np.random.default_rng(seed)
+    dims = [spec.nobs, *hidden, spec.na]
+    Ws = [rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l]) for l in range(len(dims) - 1)]
+    bs = [0.2 * rng.standard_normal(dims[l + 1]) for l in range(len(dims) - 1)]
+    Ws[-1] *= 0.8
+    return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+
+
+def policy_fmas(pol):
+    return sum(int(w.size) for w in pol.weights)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--shapes", default="affine,1x16,2x64")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import torch
+
+    import bench
+    from pcgym_amd import VecEnv, _lib, collect_rollouts
+
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    lib = _lib.load()
+    lines = [f"# tools/policy_rollout_bench.py  B={a.B} reps={a.reps}  library build {lib.pcg_build_id().decode()} "
+             f"({os.path.relpath(_lib.LIB_PATH, ROOT)})  {torch.cuda.get_device_name(0)}",
+             "# cstr, RK4 x 1, N = 60: one episode = 59 closed-loop steps; ms per episode, median of the interleaved repeats"]
+    p = bench.workload_params()
+    for name in a.shapes.split(","):
+        e_f, e_s = VecEnv(dict(p), n_envs=a.B, seed=1), VecEnv(dict(p), n_envs=a.B, seed=1)
+        spec = e_f.spec
+        pol = make_policy(spec, SHAPES[name])
+        steps = spec.N - 1
+        routes = {"fused": lambda: collect_rollouts(e_f, policy=pol), "per_step": lambda: collect_rollouts(e_s, policy=lambda o: pol(o))}
+        times = {k: [] for k in routes}
+        for rep in range(a.reps + 1):  # (pair 0 warms both routes up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                if rep == 0 and k == "fused":
+                    inside = float(((d["u"] > spec.a_low[0]) & (d["u"] < spec.a_high[0])).double().mean())
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        fm = policy_fmas(pol)
+        share = 2.0 * fm * a.B * steps / (med["fused"] * 1e-3) / FP64_VECTOR_PEAK
+        lines.append(f"{name:7s} fused {med['fused']:9.3f} ms ({us['fused']:8.2f} us/step, {a.B * steps / med['fused'] / 1e-3:.3e} env-steps/s)   "
+                     f"per-step {med['per_step']:9.3f} ms ({us['per_step']:8.2f} us/step, {a.B * steps / med['per_step'] / 1e-3:.3e} env-steps/s)   "
+                     f"per-step / fused = {med['per_step'] / med['fused']:.2f}   policy FMAs per env step {fm}, "
+                     f"= {100 * share:.1f} % of the fp64 vector peak in the fused call   actions inside the box {inside:.2f}")
+        lines.append(f"        fused repeats {[round(t, 3) for t in times['fused']]}  per-step repeats {[round(t, 3) for t in times['per_step']]}")
+        e_f.close(), e_s.close(), pol.close()
+        del e_f, e_s
+        torch.cuda.empty_cache()
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
