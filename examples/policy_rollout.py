@@ -9,6 +9,11 @@ Both return the reference's policy_eval.rollout arrays x (Nx, N, reps), u (Nu, N
 (policy_evaluation.py:71-130), reps = the env axis.  The network here is a small torch.nn.Sequential with fixed-seed
 weights standing in for a stable-baselines3 MlpPolicy's actor (Linear / Tanh / Linear / Tanh / Linear).
 
+A third section collects ON-POLICY data with the stochastic form of the same network -- stable-baselines3's MlpPolicy:
+a Gaussian actor with a state-independent log_std plus a value network -- through collect_onpolicy: sampled actions, their
+log-probabilities, values, rewards, GAE advantages and returns, again in one launch per episode (pcg_rollout_actor), and
+shows the refresh a training loop does after an optimiser step (GaussianActorCritic.update_: no device allocation).
+
 Needs an MI355X (there is no CPU path):  python examples/policy_rollout.py
 """
 import os
@@ -19,7 +24,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pcgym_amd import MLPPolicy, collect_rollouts, make_vec_env  # noqa: E402
+from pcgym_amd import GaussianActorCritic, MLPPolicy, collect_onpolicy, collect_rollouts, make_vec_env  # noqa: E402
 
 N = 60
 env_params = {
@@ -55,6 +60,42 @@ def main():
     diff = max(float((out["fused"][k] - out["per step"][k]).abs().max()) for k in ("x", "u", "r"))
     print(f"largest difference between the two routes over x, u, r: {diff:.2e} (two fp64 summation orders through a closed loop)")
     policy.close()
+    actor_critic(net, B)
+
+
+def actor_critic(actor_net, B):
+    """what PPO collects per iteration: the exploration noise is the engine's Philox stream (seed, global env index, t,
+    purpose 0x400), so a sharded run samples what the unsharded run samples"""
+    critic_net = torch.nn.Sequential(torch.nn.Linear(3, 16), torch.nn.Tanh(), torch.nn.Linear(16, 16), torch.nn.Tanh(),
+                                     torch.nn.Linear(16, 1)).double()
+    log_std = torch.nn.Parameter(torch.full((1,), -1.0, dtype=torch.float64))
+    ac = GaussianActorCritic.from_torch(actor_net, log_std, critic_net, out_map="clip", out_low=-1.0, out_high=1.0)
+    out = {}
+    for name, fused in (("per step", False), ("fused", None)):
+        env = make_vec_env(env_params, n_envs=B, seed=0)
+        collect_onpolicy(env, ac, fused=fused)  # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out[name] = d = collect_onpolicy(env, ac, gamma=0.99, lam=0.95, fused=fused)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"actor-critic, {name:8s}: {dt * 1e3:7.2f} ms per episode  obs {tuple(d['obs'].shape)} act {tuple(d['act'].shape)} "
+              f"logp {tuple(d['logp'].shape)} val {tuple(d['val'].shape)}  mean logp {d['logp'].mean().item():.3f}  "
+              f"mean return {d['rew'].sum(dim=0).mean().item():.3f}  adv std {d['adv'].std().item():.3f}")
+        env.close()
+    diff = max(float((out["fused"][k] - out["per step"][k]).abs().max()) for k in ("obs", "act", "val", "rew"))
+    same = torch.equal(out["fused"]["logp"], out["per step"]["logp"])
+    print(f"largest difference between the two routes over obs, act, val, rew: {diff:.2e}; log-probabilities bitwise equal: {same}")
+    # an "optimiser step", then the refresh: same shapes, same device blocks
+    with torch.no_grad():
+        for prm in list(actor_net.parameters()) + list(critic_net.parameters()):
+            prm.add_(0.01 * torch.randn_like(prm))
+        log_std.sub_(0.05)
+    ac.update_(actor=actor_net, log_std=log_std, critic=critic_net)
+    env = make_vec_env(env_params, n_envs=B, seed=0)
+    d = collect_onpolicy(env, ac)
+    print(f"after update_: sigma {ac.sigma[0]:.4f}, mean logp {d['logp'].mean().item():.3f}")
+    env.close(), ac.close()
 
 
 if __name__ == "__main__":

@@ -49,7 +49,7 @@ typedef unsigned long uintptr_t;
 extern "C" {
 #endif
 
-#define PCG_ABI_VERSION 15
+#define PCG_ABI_VERSION 16
 
 #ifndef PCG_API
 #define PCG_API __attribute__((visibility("default")))
@@ -493,7 +493,7 @@ typedef struct pcg_policy_cfg {
   const double* W[3];         /* host, row-major [n_next][n_prev]; layers 0 .. n_hidden             */
   const double* b[3];         /* host, [n_next]                                                     */
 } pcg_policy_cfg;
-typedef struct pcg_policy pcg_policy; /* opaque, immutable after creation */
+typedef struct pcg_policy pcg_policy; /* opaque; its weights change only through pcg_policy_update() (ABI 16) */
 
 /* Host-only validation of a policy configuration (usable without a GPU): the status pcg_policy_create() would return
  * before it touches the device.  PCG_E_DIM: n_in outside 1..PCG_MAX_NOBS, n_out outside 1..PCG_MAX_NA, n_hidden outside
@@ -503,6 +503,13 @@ PCG_API int pcg_policy_validate(const pcg_policy_cfg* cfg);
 /* Copies the weights to the current device (synchronous, a few KB).  A policy belongs to that device. */
 PCG_API int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg);
 PCG_API int pcg_policy_destroy(pcg_policy* policy);
+/* Re-uploads weights of IDENTICAL shape into the policy's existing device block (ABI 16): a training loop changes the
+ * weights every iteration and must not allocate and free device memory each time.  Synchronous, like pcg_policy_create;
+ * the caller orders it after the launches that still read the old weights (a rollout on a non-blocking stream has to be
+ * synchronised first).  activation, out_map and the clip box may change with the weights.  PCG_E_DIM when n_in, n_out,
+ * n_hidden or a width differ from the policy's; the statuses of pcg_policy_validate() for the cfg itself.  On any error
+ * the policy is unchanged. */
+PCG_API int pcg_policy_update(pcg_policy* policy, const pcg_policy_cfg* cfg);
 
 /* T env steps in ONE launch with the state in registers and the policy evaluated in the kernel between two steps:
  *   - the action of step s is policy(observation the env emitted before step s); for s = 0 that is io->obs as
@@ -523,6 +530,45 @@ PCG_API int pcg_rollout_policy(pcg_plan* plan, const pcg_buffers* io, const pcg_
                                double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
                                int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                                int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
+
+/* Closed-loop fused rollout with a STOCHASTIC actor-critic (ABI 16): what an on-policy trainer (PPO) collects, in one
+ * launch.  The form is stable-baselines3's MlpPolicy: a Gaussian actor with a state-independent standard deviation and a
+ * separate value network.  pcg_rollout_policy's loop, with this on the observation before step s (shared counter
+ * t = t0 + s):
+ *     mu   = actor's last-layer output BEFORE its output map
+ *     z_i  = standard normal, Philox keyed (seed, global env index, t, PCG_RNG_POLICY + i / 2): the engine's RNG contract,
+ *            so a sharded run (pcg_plan_set_env_offset) draws what the unsharded run draws
+ *     u_i  = fma(sigma_i, z_i, mu_i)                            the sample (what PPO's buffer keeps)
+ *     a    = out_map(u)                                         the action the env applies (PCG_POL_NONE | PCG_POL_CLIP)
+ *     logp = fma(-0.5, q, c0); q = 0, for i ascending: q = fma(z_i, z_i, q)
+ *            = log N(u; mu, sigma^2) of the UNMAPPED sample u (stable-baselines3 PPO's meaning: the env clips, the
+ *            buffer keeps u), c0 = pcg_actor_logp_const(sigma, na)
+ *     value = critic(observation): a second pcg_policy with n_out == 1 and PCG_POL_NONE, or NULL (value_out is then
+ *            not written)
+ * sigma: HOST array [na], finite and > 0; it and c0 travel by value with the launch (no device allocation, no copy).
+ * Recorded rows, each optional (NULL) and strided like a_seq_out of pcg_rollout_policy: a_seq_out [T(+1)][na][B] applied
+ * actions, u_seq_out [T(+1)][na][B] samples, logp_out [T(+1)][B], value_out [T(+1)][B].  With record_next_action, row T
+ * holds all four for the observation after the last step, drawn at counter t0 + T and not applied; its value entry is the
+ * bootstrap value.  obs_seq / rew_seq / io as in pcg_rollout_policy.
+ * Statuses, in this order, nothing launched on any of them: those of pcg_rollout_policy for the plan and the actor
+ * (PCG_E_UNSUPPORTED plans, PCG_E_DIM actor sizes); critic: PCG_E_PLAN (not a policy / another device), PCG_E_DIM
+ * (n_in != Nobs or n_out != 1), PCG_E_VALUE (an output map); PCG_E_UNSUPPORTED for an actor with PCG_POL_TANH (a squashed
+ * Gaussian needs the map's Jacobian in logp); PCG_E_NULL sigma == NULL; PCG_E_VALUE a sigma that is not finite and
+ * positive; then T / t0 / buffers / strides as in pcg_rollout_policy.
+ * Reads the plan and the policies and writes neither: safe under stream capture. */
+#define PCG_RNG_POLICY 0x400
+PCG_API int pcg_rollout_actor(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* actor, const pcg_policy* critic,
+                              const double* sigma, int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride,
+                              int64_t a_comp_stride, double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride,
+                              double* logp_out, int64_t logp_step_stride, double* value_out, int64_t value_step_stride,
+                              double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                              int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
+/* Host only: c0 = -(sum_i log sigma_i + na/2 log 2 pi), summed in ascending order in fp64 -- the constant
+ * pcg_rollout_actor passes to its kernel.  NaN for a NULL / non-positive / non-finite sigma or na outside 1..PCG_MAX_NA. */
+PCG_API double pcg_actor_logp_const(const double* sigma, int32_t na);
+/* z_out [na][B] (device): the standard normals pcg_rollout_actor draws at counter t under `seed` -- same keys, same bits --
+ * for a caller that samples outside the fused call (one pcg_step per step).  na and the env offset are the plan's. */
+PCG_API int pcg_policy_noise(pcg_plan* plan, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream);
 
 /* pcg_step followed, in the same launch, by the reset of every env that finished in it (gymnasium "same-step"
  * auto-reset: rew / done / viol are those of the finished step; x, obs, t, a_save and the per-env parameters are

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-PCG_ABI_VERSION = 15
+PCG_ABI_VERSION = 16
 PCG_MAX_NX = 24
 PCG_MAX_NA = 5
 PCG_MAX_NDM = 4
@@ -72,6 +72,7 @@ PCG_POL_NONE = 0
 PCG_POL_CLIP = 1
 PCG_POL_TANH = 2
 PCG_POL_MAX_WIDTH = 64
+PCG_RNG_POLICY = 0x400
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -202,7 +203,11 @@ EXPORTS = [
     "pcg_policy_validate",
     "pcg_policy_create",
     "pcg_policy_destroy",
+    "pcg_policy_update",
     "pcg_rollout_policy",
+    "pcg_rollout_actor",
+    "pcg_actor_logp_const",
+    "pcg_policy_noise",
     "pcg_step_autoreset",
     "pcg_graph_create",
     "pcg_graph_launch",
@@ -263,6 +268,16 @@ def declare(lib):
     lib.pcg_rollout_policy.restype = C.c_int
     lib.pcg_rollout_policy.argtypes = [vp, C.POINTER(pcg_buffers), vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int64,
                                        vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_uint64, vp]
+    lib.pcg_policy_update.restype = C.c_int
+    lib.pcg_policy_update.argtypes = [vp, C.POINTER(pcg_policy_cfg)]
+    lib.pcg_rollout_actor.restype = C.c_int
+    lib.pcg_rollout_actor.argtypes = [vp, C.POINTER(pcg_buffers), vp, vp, _pd, C.c_int32, C.c_int32,
+                                      vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64,
+                                      vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_uint64, vp]
+    lib.pcg_actor_logp_const.restype = C.c_double
+    lib.pcg_actor_logp_const.argtypes = [_pd, C.c_int32]
+    lib.pcg_policy_noise.restype = C.c_int
+    lib.pcg_policy_noise.argtypes = [vp, C.c_int64, C.c_int32, C.c_uint64, vp, vp]
     lib.pcg_step_autoreset.restype = C.c_int
     lib.pcg_step_autoreset.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_uint64, C.c_uint64, vp]
     lib.pcg_graph_create.restype = C.c_int

@@ -32,6 +32,22 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(const StepArgs A) {
   reset_env(A, c, e, A.seed);
 }
 
+// z [na][B] for one (seed, t): the bits rollout_actor_kernel (pcg_rollout_actor.hpp) draws at that counter, for the
+// per-step route (pcg_policy_noise)
+__global__ __launch_bounds__(BLOCK) void policy_noise_kernel(int64_t B, int32_t na, uint64_t seed, int64_t env_offset, uint32_t t, double* z) {
+  const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= B) return;
+#pragma unroll
+  for (int i = 0; i < PCG_MAX_NA; i += 2) {
+    if (i < na) {
+      double z0, z1;
+      rng_normal2(seed, (uint64_t)(env_offset + e), t, RNG_POLICY + (uint32_t)(i >> 1), z0, z1);
+      z[(size_t)i * B + e] = z0;
+      if (i + 1 < na) z[(size_t)(i + 1) * B + e] = z1;
+    }
+  }
+}
+
 // one table of kernel instantiations per model, built in the pcg_inst_*.hip units
 Kernels kernels_cstr(), kernels_four_tank(), kernels_me(), kernels_me_reactive(), kernels_cryst(), kernels_affine();
 Kernels kernels_complex_cstr(), kernels_disease(), kernels_batch(), kernels_photo(), kernels_cstr_series();
@@ -1529,7 +1545,9 @@ struct pcg_policy {
   uint32_t magic;
   int device;
   int n_in, n_out;
-  PolicyDev* dP;  // header + packed weights, immutable after creation
+  int n_hidden, width[2], out_map;  // the shape pcg_policy_update holds a new cfg against; the map pcg_rollout_actor asks for
+  size_t blob_doubles;              // size of the device block
+  PolicyDev* dP;  // header + packed weights; rewritten only by pcg_policy_update (same shape, same block)
 };
 static constexpr uint32_t POLICY_MAGIC = 0x50434750u;  // 'PCGP'
 
@@ -1602,7 +1620,10 @@ int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) {
   pcg_policy* q = new (std::nothrow) pcg_policy();
   if (!q) return (int)hipErrorOutOfMemory;
   q->n_in = cfg->n_in; q->n_out = cfg->n_out;
+  q->n_hidden = cfg->n_hidden; q->out_map = cfg->out_map;
+  for (int l = 0; l < 2; ++l) q->width[l] = l < cfg->n_hidden ? cfg->width[l] : 0;
   const std::vector<double> blob = pack_policy(cfg);
+  q->blob_doubles = blob.size();
   hipError_t e = hipGetDevice(&q->device);
   if (e == hipSuccess) e = hipMalloc((void**)&q->dP, sizeof(double) * blob.size());
   if (e == hipSuccess) e = hipMemcpy(q->dP, blob.data(), sizeof(double) * blob.size(), hipMemcpyHostToDevice);
@@ -1614,6 +1635,27 @@ int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) {
   q->magic = POLICY_MAGIC;
   *out = q;
   return PCG_OK;
+}
+
+int pcg_policy_update(pcg_policy* q, const pcg_policy_cfg* cfg) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC) return PCG_E_PLAN;
+  PCG_TRY(pcg_policy_validate(cfg));
+  if (cfg->n_in != q->n_in || cfg->n_out != q->n_out || cfg->n_hidden != q->n_hidden) return PCG_E_DIM;
+  for (int l = 0; l < cfg->n_hidden; ++l)
+    if (cfg->width[l] != q->width[l]) return PCG_E_DIM;
+  const std::vector<double> blob = pack_policy(cfg);
+  if (blob.size() != q->blob_doubles) return PCG_E_DIM;  // (cannot happen: the block's size is a function of the shape)
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != q->device) HIP_TRY(hipSetDevice(q->device));
+  hipError_t e = hipMemcpy(q->dP, blob.data(), sizeof(double) * blob.size(), hipMemcpyHostToDevice);
+  if (dev != q->device) {
+    const hipError_t e2 = hipSetDevice(dev);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e == hipSuccess) q->out_map = cfg->out_map;
+  return (int)e;
 }
 
 int pcg_policy_destroy(pcg_policy* q) {
@@ -1657,6 +1699,84 @@ int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, 
   pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
   pa.record_next = record_next_action ? 1 : 0;
   hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, pa);
+  return (int)hipGetLastError();
+}
+
+// ---- ... with a Gaussian actor and an optional critic (pcg_rollout_actor.hpp) -------------------------------------------
+// c0 of log N(u; mu, sigma^2) = c0 - q / 2: the one place this constant is formed (GaussianActorCritic.logp_const reads it
+// here, so that the host restatement of the kernel's logp holds the kernel's own bits)
+double pcg_actor_logp_const(const double* sigma, int32_t na) {
+  if (!sigma || na < 1 || na > PCG_MAX_NA) return std::nan("");
+  double s = 0.0;
+  for (int i = 0; i < na; ++i) {
+    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return std::nan("");
+    s += std::log(sigma[i]);
+  }
+  const double half_log_2pi = 0.91893853320467274178;
+  return -(s + (double)na * half_log_2pi);
+}
+
+int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, const pcg_policy* v, const double* sigma,
+                      int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                      double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride, double* logp_out,
+                      int64_t logp_step_stride, double* value_out, int64_t value_step_stride, double* obs_seq,
+                      int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                      int32_t record_next_action, uint64_t seed, void* stream) {
+  StepArgs a;
+  int rc = fill_args(p, io, &a);
+  if (rc != PCG_OK) return rc;
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  const DevConst& c = p->hc;
+  const int ls = lean_scheme(p->integrator_id);  // (the plans pcg_rollout_policy takes, asked in its order)
+  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
+  const ActFn fn = kernels(p->kid).roll_actor[ls];
+  if (!fn) return PCG_E_UNSUPPORTED;
+  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  if (v) {
+    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
+    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
+    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
+  }
+  // a squashed Gaussian's density carries the map's Jacobian: not this call
+  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
+  if (!sigma) return PCG_E_NULL;
+  for (int i = 0; i < c.na; ++i)
+    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  if (T < 1 || t0 < 0 || (int64_t)t0 + (int64_t)T > 0x7fffffffLL) return PCG_E_VALUE;
+  if (io->B == 0) return PCG_OK;
+  if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
+  if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
+  if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
+  if ((a_seq_out && a_comp_stride < io->B) || (u_seq_out && u_comp_stride < io->B) || (obs_seq && obs_comp_stride < io->B))
+    return PCG_E_DIM;
+  a.t_scalar = t0; a.seed = seed; a.T = T;
+  a.d = nullptr;
+  a.obs_seq = obs_seq; a.rew_seq = rew_seq;
+  a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride; a.r_ss = rew_step_stride;
+  ActorArgs aa;
+  std::memset(&aa, 0, sizeof(aa));
+  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
+  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
+  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
+  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
+  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
+  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
+  aa.c0 = pcg_actor_logp_const(sigma, c.na);
+  aa.record_next = record_next_action ? 1 : 0;
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, aa);
+  return (int)hipGetLastError();
+}
+
+int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {
+  if (!plan_ok(p)) return PCG_E_PLAN;
+  if (B < 0) return PCG_E_DIM;
+  if (t < 0) return PCG_E_VALUE;
+  if (B == 0) return PCG_OK;
+  if (!z_out) return PCG_E_NULL;
+  hipLaunchKernelGGL(cov(policy_noise_kernel), dim3(grid_for(B)), dim3(BLOCK), 0, (hipStream_t)stream, B, (int32_t)p->hc.na, seed,
+                     p->env_offset, (uint32_t)t, z_out);
   return (int)hipGetLastError();
 }
 

@@ -1733,6 +1733,7 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_flat.hpp"
 #ifndef __HIPCC_RTC__  // (ahead-of-time kernels only: a run-time compiled plan has no closed-loop rollout)
 #include "pcg_rollout_policy.hpp"
+#include "pcg_rollout_actor.hpp"
 #endif
 namespace pcg {
 
@@ -1745,6 +1746,7 @@ using StepFn = void (*)(const StepArgs);
 using RhsKFn = void (*)(CDevConst*, int64_t, int, const double*, const double*, double*);
 using IntKFn = void (*)(CDevConst*, int64_t, int, double*, const double*, int32_t*);
 using PolFn = void (*)(const StepArgs, const PolicyArgs);
+using ActFn = void (*)(const StepArgs, const ActorArgs);
 
 // one instantiation of the feature-masked small-model kernel (pcg_step_feat.hpp): serves every launch whose
 // needs are a subset of `mask`
@@ -1788,6 +1790,7 @@ struct Kernels {
   StepFn rollout_unc[PCG_INT_COUNT]; // fused rollout with per-env parameters (RK4, DOPRI5; null for affine)
   StepFn roll_hot;                   // second pass of the barrier-free rollout of a PCG_INT_T5G plan (models with a guard)
   PolFn roll_policy[2];              // closed-loop fused rollout with an on-device MLP policy [lean_scheme(integrator)]
+  ActFn roll_actor[2];               // ... with a Gaussian actor (sampled action, log-prob) and an optional critic
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1850,6 +1853,8 @@ Kernels make_kernels() {
   // closed-loop fused rollout (pcg_rollout_policy.hpp): the two fixed-step schemes, beside their open-loop kernels
   k.roll_policy[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel<M, PCG_INT_RK4>;
   k.roll_policy[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_actor[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel<M, PCG_INT_RK4>;
+  k.roll_actor[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel<M, PCG_INT_CV8>;
   // Tsit5 (the reference's jax method): general kernel, both counter modes, and the integration hook
   k.step[PCG_INT_TSIT5][0][0][0] = k.step[PCG_INT_TSIT5][0][0][1] = step_kernel<M, PCG_INT_TSIT5, false, false, true>;
   k.step[PCG_INT_TSIT5][1][0][0] = k.step[PCG_INT_TSIT5][1][0][1] = step_kernel<M, PCG_INT_TSIT5, true, false, true>;

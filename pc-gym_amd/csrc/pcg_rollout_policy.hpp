@@ -106,14 +106,14 @@ PCG_DEV void pol_rows_from_h(const PCG_CONSTANT PolicyDev& P, const PCG_CONSTANT
   }
 }
 
-// a = policy(in).  NIN: a multiple of POL_IB that holds the plan's observation vector (entries past n_in are zero);
-// NA: the kernel's action width (rows past n_out are zero: the output matrix is padded to PCG_MAX_NA rows).
+// out = the last layer's output BEFORE the output map (the mean of a Gaussian actor, a critic's value:
+// pcg_rollout_actor.hpp).  NIN: a multiple of POL_IB that holds the plan's observation vector (entries past n_in are zero);
+// NA: the kernel's output width (rows past n_out are zero: the output matrix is padded to PCG_MAX_NA rows).
 template <int NIN, int NA>
-PCG_DEV void policy_eval(const PCG_CONSTANT PolicyDev& P, const double (&in)[NIN], double (&a)[NA]) {
-  static_assert(NIN % POL_IB == 0 && NA <= PCG_MAX_NA, "policy_eval: block sizes");
+PCG_DEV void policy_raw(const PCG_CONSTANT PolicyDev& P, const double (&in)[NIN], double (&out)[NA]) {
+  static_assert(NIN % POL_IB == 0 && NA <= PCG_MAX_NA, "policy_raw: block sizes");
   const PCG_CONSTANT double* D = reinterpret_cast<const PCG_CONSTANT double*>(&P + 1);
   const int nh = P.n_hidden;
-  double out[NA];
   if (nh == 0) {
     const int ld = P.ld[0], n_in = P.n_in;
     const PCG_CONSTANT double* W = D + P.offW[0];
@@ -154,6 +154,11 @@ PCG_DEV void policy_eval(const PCG_CONSTANT PolicyDev& P, const double (&in)[NIN
       }
     }
   }
+}
+
+// a = out_map(out): the policy's output map, component by component
+template <int NA>
+PCG_DEV void policy_map(const PCG_CONSTANT PolicyDev& P, const double (&out)[NA], double (&a)[NA]) {
   const int om = P.out_map;
   const double lo = P.out_lo, hi = P.out_hi;
 #pragma unroll
@@ -163,6 +168,14 @@ PCG_DEV void policy_eval(const PCG_CONSTANT PolicyDev& P, const double (&in)[NIN
     else if (om == PCG_POL_TANH) v = tanh(v);
     a[o] = v;
   }
+}
+
+// a = policy(in) = out_map(raw output)
+template <int NIN, int NA>
+PCG_DEV void policy_eval(const PCG_CONSTANT PolicyDev& P, const double (&in)[NIN], double (&a)[NA]) {
+  double out[NA];
+  policy_raw<NIN, NA>(P, in, out);
+  policy_map<NA>(P, out, a);
 }
 
 // the observation vector of one step in store_obs order [ox | osp | od], zero beyond it

@@ -330,6 +330,53 @@ class VecEnv:
         self.t += T
         return a_seq, obs_seq, rew_seq
 
+    def rollout_actor(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
+                      collect_logp=True, collect_values=True, record_next_action=False):
+        """Fused closed-loop rollout with a stochastic actor-critic (:class:`~pcgym_amd.policy.GaussianActorCritic`): T steps
+        in one launch; per step the kernel draws ``u = mu(obs) + sigma z`` (z: Philox keyed (seed, global env index, t,
+        purpose 0x400), the bits ``policy_noise`` returns), applies ``a = out_map(u)``, and records ``log N(u; mu, sigma^2)`` and
+        the critic's value of the same observation.  Returns a dict of the recorded arrays (None where not asked for, "val"
+        None without a critic): "a" / "u" (T [+1], na, B), "logp" / "val" (T [+1], B), "obs" (T, Nobs, B), "rew" (T, B).  With
+        ``record_next_action`` row T holds the four quantities for the observation after the last step (drawn at counter
+        t + T, not applied): its value is the bootstrap value.  Plans / networks the kernel does not take raise PcgError."""
+        torch = _torch()
+        if self.per_env_t:
+            raise ValueError("rollout_actor() is lock-stepped only")
+        s, f64, dev, B = self.spec, torch.float64, self.device, self.B
+        T = int(T)
+        R = T + (1 if record_next_action else 0)
+        collect_values = collect_values and ac.critic is not None
+        a_seq = torch.empty((R, s.na, B), dtype=f64, device=dev) if collect_actions else None
+        u_seq = torch.empty((R, s.na, B), dtype=f64, device=dev) if collect_samples else None
+        lp = torch.empty((R, B), dtype=f64, device=dev) if collect_logp else None
+        val = torch.empty((R, B), dtype=f64, device=dev) if collect_values else None
+        obs_seq = torch.empty((T, s.nobs, B), dtype=f64, device=dev) if collect_obs else None
+        rew_seq = torch.empty((T, B), dtype=f64, device=dev) if collect_rew else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_actor(
+            self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
+            ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
+            ptr(a_seq), s.na * B, B, ptr(u_seq), s.na * B, B, ptr(lp), B, ptr(val), B,
+            ptr(obs_seq), s.nobs * B, B, ptr(rew_seq), B,
+            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_actor")
+        self.t += T
+        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
+
+    def policy_noise(self, t=None, out=None):
+        """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the
+        current episode -- same Philox keys, same bits -- for a caller that samples outside the kernel."""
+        torch = _torch()
+        if self.per_env_t:
+            raise ValueError("policy_noise() is lock-stepped only")
+        t = self.t if t is None else int(t)
+        z = out if out is not None else torch.empty((self.spec.na, self.B), dtype=torch.float64, device=self.device)
+        if z.shape != (self.spec.na, self.B) or z.dtype != torch.float64 or not z.is_contiguous() or z.device != self.obs_soa.device:
+            raise ValueError(f"policy_noise: need a contiguous float64 tensor of shape ({self.spec.na}, {self.B}) on {self.device}")
+        _lib.check(self._lib.pcg_policy_noise(self._plan, self.B, t, self._episode_seed(), z.data_ptr(), self._stream()),
+                   "pcg_policy_noise")
+        return z
+
     def capture_steps(self, actions, disturbances=None, with_reset=False):
         """Record ``len(actions)`` consecutive step() launches (starting at the current ``t``, or at a
         full reset if ``with_reset``) as one HIP graph over this env's buffers.

@@ -59,7 +59,8 @@ class MLPPolicy:
         self._handles = {}   # device index -> pcg_policy*
 
     # ---- the callable: torch fp64 on the observation's device ----------------------------------------------------------
-    def __call__(self, obs):
+    def raw(self, obs):
+        """the last layer's output BEFORE the output map (the mean of a Gaussian actor, a critic's value)"""
         torch = _torch()
         obs = torch.as_tensor(obs)
         key = str(obs.device)
@@ -72,11 +73,39 @@ class MLPPolicy:
             h = torch.addmm(b, h, w.t())
             if l < self.n_hidden:
                 h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
+        return h
+
+    def map(self, h):
+        """the output map alone: what turns ``raw(obs)`` into the policy's output"""
+        torch = _torch()
         if self.out_map == "clip":
             h = torch.clamp(h, self.out_low, self.out_high)
         elif self.out_map == "tanh":
             h = torch.tanh(h)
         return h
+
+    def __call__(self, obs):
+        return self.map(self.raw(obs))
+
+    def update_(self, weights, biases):
+        """New weights of IDENTICAL shape, in place: the host arrays, the cached torch tensors and every live device handle
+        (``pcg_policy_update``: the device block is rewritten, nothing is allocated or freed).  A shape change raises
+        ValueError and leaves the policy as it was."""
+        ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)) for w in weights]
+        bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1)) for b in biases]
+        if [w.shape for w in ws] != [w.shape for w in self.weights] or [b.shape for b in bs] != [b.shape for b in self.biases]:
+            raise ValueError(f"update_ keeps the shape: {[w.shape for w in self.weights]}, not {[w.shape for w in ws]}")
+        old = (self.weights, self.biases)
+        self.weights, self.biases = ws, bs
+        cfg, keep = self.to_cfg()
+        rc = int(_lib.load().pcg_policy_validate(C.byref(cfg)))
+        if rc != 0:
+            self.weights, self.biases = old
+            _lib.check(rc, "pcg_policy_validate")
+        self._tensors = {}
+        for h in self._handles.values():
+            _lib.check(_lib.load().pcg_policy_update(h, C.byref(cfg)), "pcg_policy_update")
+        return self
 
     @classmethod
     def from_torch(cls, module, out_map=None, out_low=-1.0, out_high=1.0):
@@ -169,3 +198,134 @@ def fused_policy_ok(spec, policy):
     return (isinstance(policy, MLPPolicy) and spec.integrator in ("rk4", "cv8") and not spec.ncon and not spec.nunc
             and spec.user_rhs_src is None and not spec.user_reward_src and not spec.user_cons_src
             and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
+
+
+def _module_arrays(module):
+    """(weights, biases) of an ``nn.Sequential`` through MLPPolicy.from_torch's reading of it"""
+    pol = MLPPolicy.from_torch(module, out_map="none")
+    return pol.weights, pol.biases
+
+
+class GaussianActorCritic:
+    """stable-baselines3's ``MlpPolicy`` as data: a Gaussian actor with a state-independent ``log_std`` plus an optional
+    separate value network -- what ``pcg_rollout_actor`` evaluates inside the rollout kernel (include/pcgym_hip.h).
+
+    actor   : :class:`MLPPolicy` whose ``raw`` output is the mean ``mu``; its output map ("none" | "clip") turns the sample
+              ``u = mu + sigma z`` into the action the env applies.  "tanh" is refused: a squashed Gaussian's density needs
+              the map's Jacobian.
+    log_std : (na,) array (a scalar is broadcast).  ``sigma = exp(log_std)``; ``logp_const`` = -(sum log sigma + na/2 log 2 pi)
+              is read from the library (``pcg_actor_logp_const``), so that it is the kernel's own constant bit for bit.
+    critic  : :class:`MLPPolicy` with ``n_out == 1``, ``out_map="none"`` and the actor's ``n_in``, or None.
+
+    ``log_prob`` is the log-density of the UNMAPPED sample ``u`` under N(mu, sigma^2) -- stable-baselines3 PPO's meaning: the
+    env clips, the buffer keeps ``u``.  The torch methods work in fp64 on the observation's device (CPU included), with the
+    kernel's formulas and summation order (components ascending)."""
+
+    def __init__(self, actor, log_std, critic=None):
+        if not isinstance(actor, MLPPolicy):
+            raise ValueError(f"actor must be an MLPPolicy, not {type(actor).__name__}")
+        if actor.out_map == "tanh":
+            raise ValueError("a tanh output map makes a squashed Gaussian, whose log-probability needs the map's Jacobian: "
+                             "use out_map='none' or 'clip'")
+        if critic is not None:
+            if not isinstance(critic, MLPPolicy):
+                raise ValueError(f"critic must be an MLPPolicy, not {type(critic).__name__}")
+            if critic.n_out != 1 or critic.out_map != "none":
+                raise ValueError(f"the critic has one output and no output map (n_out={critic.n_out}, out_map={critic.out_map!r})")
+            if critic.n_in != actor.n_in:
+                raise ValueError(f"the critic reads {critic.n_in} inputs, the actor {actor.n_in}")
+        self.actor, self.critic = actor, critic
+        self.n_in, self.n_out = actor.n_in, actor.n_out
+        self._set_log_std(log_std)
+
+    def _set_log_std(self, log_std):
+        if hasattr(log_std, "detach"):
+            log_std = log_std.detach().cpu().double().numpy()
+        ls = np.asarray(log_std, dtype=np.float64)
+        if ls.ndim == 0:
+            ls = np.full(self.n_out, float(ls))
+        ls = np.ascontiguousarray(ls.reshape(-1))
+        if ls.shape != (self.n_out,):
+            raise ValueError(f"log_std has {ls.size} entries, the actor {self.n_out} outputs")
+        sigma = np.exp(ls)
+        if not (np.isfinite(sigma).all() and (sigma > 0).all()):
+            raise ValueError("exp(log_std) must be finite and positive")
+        c0 = float(_lib.load().pcg_actor_logp_const(sigma.ctypes.data_as(C.POINTER(C.c_double)), self.n_out))
+        if not np.isfinite(c0):
+            raise ValueError(f"no log-probability constant for sigma = {sigma} ({self.n_out} outputs)")
+        self.log_std, self.sigma, self.logp_const = ls, sigma, c0
+        self._sig_t = {}
+
+    def _sigma_on(self, device):
+        key = str(device)
+        if key not in self._sig_t:
+            self._sig_t[key] = _torch().as_tensor(self.sigma, device=device)
+        return self._sig_t[key]
+
+    # ---- torch fp64, any device ------------------------------------------------------------------------------------------
+    def mean(self, obs):
+        """mu (B, na)"""
+        return self.actor.raw(obs)
+
+    def sample(self, obs, z):
+        """u = mu + sigma z (B, na) for standard normals z (B, na)"""
+        mu = self.mean(obs)
+        return _torch().addcmul(mu, self._sigma_on(mu.device), z.to(mu.dtype))
+
+    def action(self, u):
+        """the action the env applies for the sample u: the actor's output map"""
+        return self.actor.map(u)
+
+    def log_prob(self, obs, u):
+        """log N(u; mu(obs), sigma^2), (B,): c0 - q / 2 with q the sum of the squared standardised residuals, ascending"""
+        mu = self.mean(obs)
+        z = (_torch().as_tensor(u, device=mu.device).to(mu.dtype) - mu) / self._sigma_on(mu.device)
+        return self.log_prob_z(z)
+
+    def log_prob_z(self, z):
+        """the same from the standard normals themselves (B, na) -> (B,): the kernel's statement, fma(-0.5, q, c0)"""
+        q = z[:, 0] * z[:, 0]
+        for i in range(1, self.n_out):
+            q = q + z[:, i] * z[:, i]
+        return self.logp_const - 0.5 * q
+
+    def value(self, obs):
+        """critic(obs) (B,)"""
+        if self.critic is None:
+            raise ValueError("this actor-critic has no critic")
+        return self.critic.raw(obs)[:, 0]
+
+    @classmethod
+    def from_torch(cls, actor_seq, log_std, critic_seq=None, out_map=None, out_low=-1.0, out_high=1.0):
+        """From the ``nn.Sequential`` of the actor (MLPPolicy.from_torch's forms; ``out_map`` defaults to "clip"), its
+        ``log_std`` (tensor, Parameter or array) and, optionally, the ``nn.Sequential`` of the value network."""
+        actor = MLPPolicy.from_torch(actor_seq, out_map=out_map, out_low=out_low, out_high=out_high)
+        critic = MLPPolicy.from_torch(critic_seq, out_map="none") if critic_seq is not None else None
+        return cls(actor, log_std, critic)
+
+    def update_(self, actor=None, log_std=None, critic=None):
+        """Refresh after an optimiser step, in place: ``actor`` / ``critic`` are ``nn.Sequential`` modules or
+        ``(weights, biases)`` pairs of the SAME shapes, ``log_std`` as in the constructor.  Host arrays and every live device
+        handle follow (``pcg_policy_update``: no device allocation); a shape change raises ValueError."""
+        for pol, new in ((self.actor, actor), (self.critic, critic)):
+            if new is None:
+                continue
+            if pol is None:
+                raise ValueError("this actor-critic has no critic to update")
+            w, b = new if isinstance(new, (tuple, list)) else _module_arrays(new)
+            pol.update_(w, b)
+        if log_std is not None:
+            self._set_log_std(log_std)
+        return self
+
+    def close(self):
+        self.actor.close()
+        if self.critic is not None:
+            self.critic.close()
+
+
+def fused_actor_ok(spec, ac):
+    """the plans and networks pcg_rollout_actor takes: those of pcg_rollout_policy for the actor, no tanh map, and a critic
+    (if any) of the plan's observation size that the device form can hold"""
+    return (isinstance(ac, GaussianActorCritic) and fused_policy_ok(spec, ac.actor) and ac.actor.out_map != "tanh"
+            and (ac.critic is None or (ac.critic.n_in == spec.nobs and ac.critic.validate() == 0)))

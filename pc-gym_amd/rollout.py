@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .policy import fused_policy_ok
+from .policy import fused_actor_ok, fused_policy_ok
 
 
 def _torch():
@@ -151,6 +151,97 @@ def collect_rollouts(env, policy=None, actions=None):
     if g is not None:
         out["g"] = g
     return out
+
+
+def gae(rew, val, gamma=0.99, lam=0.95, bootstrap_last=False):
+    """Generalised advantage estimation over one episode for all envs at once (Schulman et al. 2016; stable-baselines3's
+    ``RolloutBuffer.compute_returns_and_advantage``): rew (T, B), val (T + 1, B) -> (adv (T, B), ret (T, B)).
+
+        delta_t = rew_t + gamma val_{t+1} - val_t;   adv_t = delta_t + gamma lam adv_{t+1};   ret_t = adv_t + val_t
+
+    ``val[T]`` is the value of the observation after the last step.  ``bootstrap_last=False`` treats the episode's end as
+    terminal (val[T] does not enter); ``True`` bootstraps from it (a time-limit truncation)."""
+    torch = _torch()
+    T = rew.shape[0]
+    if val.shape[0] != T + 1 or val.shape[1:] != rew.shape[1:]:
+        raise ValueError(f"gae: rew {tuple(rew.shape)} needs val of shape ({T + 1}, ...), not {tuple(val.shape)}")
+    adv = torch.empty_like(rew)
+    last = torch.zeros_like(rew[0])
+    for t in range(T - 1, -1, -1):
+        nxt = val[t + 1] if (t < T - 1 or bootstrap_last) else torch.zeros_like(val[t])
+        delta = rew[t] + gamma * nxt - val[t]
+        last = delta + gamma * lam * last
+        adv[t] = last
+    return adv, adv + val[:T]
+
+
+def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None):
+    """One episode (N - 1 steps) of all B envs under the stochastic actor-critic ``ac`` (a
+    :class:`~pcgym_amd.policy.GaussianActorCritic` with a critic): what an on-policy trainer such as PPO collects.
+
+    Returns a dict of device tensors, step-major, in POLICY space (what the networks read and emit, not physical units):
+        obs  (N, Nobs, B)  the policy's inputs, row 0 the reset observation
+        act  (N-1, na, B)  the UNMAPPED samples u = mu + sigma z (the env applied out_map(u))
+        logp (N-1, B)      log N(u; mu, sigma^2)
+        val  (N, B)        critic values of obs; row N-1 is the bootstrap value
+        rew  (N-1, B)
+        adv, ret (N-1, B)  from :func:`gae`
+
+    Route: ONE launch (``pcg_rollout_actor``) when the plan and the networks qualify (``fused_actor_ok``: RK4 / CV8, no
+    constraint rows, no per-env parameters, no user model, no tanh map); otherwise -- or with ``fused=False`` -- one
+    ``env.step`` per step with the sample formed in torch from ``env.policy_noise``, i.e. from the same random bits."""
+    torch = _torch()
+    s = env.spec
+    B, N, dev, f64 = env.B, s.N, env.device, torch.float64
+    if env.per_env_t:
+        raise ValueError("collect_onpolicy needs a lock-stepped VecEnv")
+    if ac.critic is None:
+        raise ValueError("collect_onpolicy needs a critic: the advantages are estimated from its values")
+    if ac.n_in != s.nobs or ac.n_out != s.na:
+        raise ValueError(f"the actor maps {ac.n_in} -> {ac.n_out}, the env {s.nobs} -> {s.na}")
+    T = N - 1
+    obs = torch.empty((N, s.nobs, B), dtype=f64, device=dev)
+    act = torch.empty((T, s.na, B), dtype=f64, device=dev)
+    logp = torch.empty((N, B), dtype=f64, device=dev)
+    val = torch.empty((N, B), dtype=f64, device=dev)
+    rew = torch.empty((T, B), dtype=f64, device=dev)
+    o, _ = env.reset()
+    obs[0] = env.obs_soa
+    ok = fused_actor_ok(s, ac)
+    if fused and not ok:
+        raise ValueError("this plan / actor-critic does not qualify for the fused call")
+    if ok and fused is not False:
+        # (row N-1 of the samples is drawn and dropped: only its value, the bootstrap value, is kept)
+        u = torch.empty((N, s.na, B), dtype=f64, device=dev)
+        env._buf.d = None
+        rc = env._lib.pcg_rollout_actor(
+            env._plan, env._bufp, ac.actor.handle(dev), ac.critic.handle(dev), ac.sigma.ctypes.data_as(C.POINTER(C.c_double)),
+            0, T, None, 0, 0, u.data_ptr(), s.na * B, B, logp.data_ptr(), B, val.data_ptr(), B,
+            obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_actor")
+        env.t += T
+        act = u[:T]
+    else:
+        saved = (env.obs_soa, env.rew)
+        z = torch.empty((s.na, B), dtype=f64, device=dev)
+        try:
+            for i in range(T):
+                env.policy_noise(i, out=z)
+                zt = z.t()
+                u = ac.sample(o, zt)
+                act[i] = u.t()
+                logp[i] = ac.log_prob_z(zt)
+                val[i] = ac.value(o)
+                env.bind_outputs(obs[i + 1], rew[i])
+                o, _, _, _, _ = env.step(ac.action(u))
+            val[T] = ac.value(o)
+        finally:
+            last_o, last_r = env.obs_soa, env.rew
+            env.bind_outputs(*saved)
+            env.obs_soa.copy_(last_o)
+            env.rew.copy_(last_r)
+    adv, ret = gae(rew, val, gamma, lam, bootstrap_last)
+    return {"obs": obs, "act": act, "logp": logp[:T], "val": val, "rew": rew, "adv": adv, "ret": ret}
 
 
 class reproducibility_metric:

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""On-policy data collection with a stochastic actor-critic: the fused call (pcg_rollout_actor: actor, Gaussian sample,
+log-probability and critic evaluated in the rollout kernel) against the per-step route with the same networks, and against
+the deterministic fused call (pcg_rollout_policy) with the same actor.
+
+    python tools/actor_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--out FILE]
+
+Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s).  Four routes alternate inside one process
+(`reps` rounds after one warm-up round); times are device-event times of whole episodes (reset included), the figure
+compared is the median:
+    a   collect_onpolicy(env, ac)                fused, actor + critic of the same hidden shape, GAE included
+    b   collect_onpolicy(env, ac, fused=False)   its per-step route: pcg_policy_noise + torch networks + pcg_step per step
+    c   collect_rollouts(env, policy=ac.actor)   the deterministic fused call, same actor
+    a0  reset + VecEnv.rollout_actor without a critic (samples, log-probabilities, observations, rewards recorded)
+The condition: a is not slower than b for any shape (collect_onpolicy takes the fused call wherever the plan qualifies).
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
+
+from policy_rollout_bench import SHAPES, make_policy, policy_fmas  # noqa: E402
+
+
+def make_ac(spec, hidden, critic=True, seed=17):
+    """policy_rollout_bench's actor, sigma = exp(-1.5) (0.22 of the normalised action half width), a critic of the same shape"""
+    from pcgym_amd import GaussianActorCritic, MLPPolicy
+
+    actor = make_policy(spec, hidden, seed)
+    cr = None
+    if critic:
+        c = make_policy(spec, hidden, seed + 100)
+        cr = MLPPolicy(c.weights[:-1] + [c.weights[-1][:1]], c.biases[:-1] + [c.biases[-1][:1]], activation="tanh", out_map="none")
+    return GaussianActorCritic(actor, np.full(spec.na, -1.5), cr)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--shapes", default="affine,1x16,2x64")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import torch
+
+    import bench
+    from pcgym_amd import VecEnv, _lib, collect_onpolicy, collect_rollouts
+
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    lib = _lib.load()
+    lines = [f"# tools/actor_rollout_bench.py  B={a.B} reps={a.reps}  library build {lib.pcg_build_id().decode()} "
+             f"({os.path.relpath(_lib.LIB_PATH, ROOT)})  {torch.cuda.get_device_name(0)}",
+             "# cstr, RK4 x 1, N = 60: one episode = 59 closed-loop steps; us per step, median of the interleaved repeats",
+             "# a = collect_onpolicy fused (actor + critic), b = its per-step route, c = deterministic pcg_rollout_policy "
+             "(same actor), a0 = fused without a critic"]
+    p = bench.workload_params()
+    for name in a.shapes.split(","):
+        envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("a", "b", "c", "a0")}
+        spec = envs["a"].spec
+        ac, ac0 = make_ac(spec, SHAPES[name]), make_ac(spec, SHAPES[name], critic=False)
+        steps = spec.N - 1
+
+        def no_critic():
+            envs["a0"].reset()
+            return envs["a0"].rollout_actor(ac0, steps, collect_obs=True, record_next_action=True)
+
+        routes = {"a": lambda: collect_onpolicy(envs["a"], ac), "b": lambda: collect_onpolicy(envs["b"], ac, fused=False),
+                  "c": lambda: collect_rollouts(envs["c"], policy=ac.actor), "a0": no_critic}
+        times = {k: [] for k in routes}
+        clipped = float("nan")
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                if rep == 0 and k == "a":
+                    clipped = float(((d["act"] < -1.0) | (d["act"] > 1.0)).double().mean())
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        fm_a, fm_c = policy_fmas(ac.actor), policy_fmas(ac.critic)
+        verdict = "fused not slower than per-step" if med["a"] <= med["b"] else "FUSED SLOWER THAN PER-STEP"
+        lines.append(f"{name:7s} a {us['a']:8.2f}  b {us['b']:8.2f}  c {us['c']:8.2f}  a0 {us['a0']:8.2f} us/step   "
+                     f"a / b = {med['a'] / med['b']:.3f} (b / a = {med['b'] / med['a']:.2f})   a / c = {med['a'] / med['c']:.3f}   "
+                     f"a0 / c = {med['a0'] / med['c']:.3f}   {a.B * steps / med['a'] / 1e-3:.3e} env-steps/s fused   "
+                     f"FMAs per env step: actor {fm_a}, critic {fm_c}   samples clipped {clipped:.3f}   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        ac.close(), ac0.close()
+        del envs
+        torch.cuda.empty_cache()
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -137,7 +137,7 @@ def covering_tests():
     """mangled kernel name -> one passing test of the GPU suite that launched it against the oracle / a fixture (the record
     tools/kernel_coverage.py condensed from the last full GPU run, committed under profiles/)"""
     out = {}
-    for rnd in ("r6", "r7"):  # (a later round's record adds the kernels it brought and overrides what it re-ran)
+    for rnd in ("r6", "r7", "r8"):  # (a later round's record adds the kernels it brought and overrides what it re-ran)
         p = os.path.join(ROOT, "profiles", rnd, "kernel_tests.json")
         if os.path.exists(p):
             with open(p) as f:
@@ -167,7 +167,7 @@ def main():
     if a.scratch:
         tests = covering_tests()
         print("\nkernels with scratch > 0: bytes per lane; registers (of them accumulation); scalar / vector spills; the kernel; "
-              "a passing oracle test that launches it (profiles/r6 + r7/kernel_tests.json)")
+              "a passing oracle test that launches it (profiles/r6 + r7 + r8/kernel_tests.json)")
         for k in sorted((k for k in ks if k["scratch"] > 0), key=lambda k: -k["scratch"]):
             print(f"{k['scratch']:7d} {k['vgpr']:4d} ({k['agpr']:3d}) {k['sgpr_spill']:5d}/{k['vgpr_spill']:<5d} {k['demangled']}   <- "
                   f"{tests.get(k['name'], 'NO COVERING TEST RECORDED')}")
