@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include <fstream>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -1667,39 +1668,74 @@ int pcg_policy_destroy(pcg_policy* q) {
   return (int)e;
 }
 
+// Both closed-loop entry points validate through these two: closed_loop_open up to the policy's size, then what is the entry
+// point's own (the actor: critic, tanh map, sigma), then closed_loop_launch from the step range on.  (Templates over the
+// kernel's function and argument types: C++ linkage inside this file's extern "C".)
+extern "C++" {
+struct ClosedLoopRun {  // what both entry points are given beside their networks: step range, the env's recorded sequences, seed
+  int32_t t0, T;
+  double* obs_seq;
+  int64_t obs_ss, obs_cs;  // element strides (step, component)
+  double* rew_seq;
+  int64_t rew_ss;
+  uint64_t seed;
+};
+struct SeqRec {  // a sequence the head records, with its component stride; null: not recorded
+  const double* seq;
+  int64_t comp_stride;
+};
+
+template <class Fn>
+static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2], StepArgs* a,
+                            Fn* fn) {
+  PCG_TRY(fill_args(p, io, a));
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  const DevConst& c = p->hc;
+  // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, run-time compiled
+  // models / expressions, and every integrator but the two fixed-step schemes
+  const int ls = lean_scheme(p->integrator_id);
+  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
+  *fn = (kernels(p->kid).*table)[ls];
+  if (!*fn) return PCG_E_UNSUPPORTED;
+  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  return PCG_OK;
+}
+
+template <class Fn, class HeadArgs>
+static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, Fn fn, const HeadArgs& head, const ClosedLoopRun& r,
+                              std::initializer_list<SeqRec> head_recs, void* stream) {
+  const DevConst& c = p->hc;
+  if (r.T < 1 || r.t0 < 0 || (int64_t)r.t0 + (int64_t)r.T > 0x7fffffffLL) return PCG_E_VALUE;
+  if (io->B == 0) return PCG_OK;
+  if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
+  if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
+  if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
+  if (r.obs_seq && r.obs_cs < io->B) return PCG_E_DIM;
+  for (const SeqRec& h : head_recs)
+    if (h.seq && h.comp_stride < io->B) return PCG_E_DIM;
+  a.t_scalar = r.t0; a.seed = r.seed; a.T = r.T;
+  a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
+  a.obs_seq = r.obs_seq; a.rew_seq = r.rew_seq;
+  a.o_ss = r.obs_ss; a.o_cs = r.obs_cs; a.r_ss = r.rew_ss;
+  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head);
+  return (int)hipGetLastError();
+}
+}  // extern "C++"
+
 int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
                        int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
                        int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
                        uint64_t seed, void* stream) {
   StepArgs a;
-  int rc = fill_args(p, io, &a);
-  if (rc != PCG_OK) return rc;
-  if (!q) return PCG_E_NULL;
-  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
-  const DevConst& c = p->hc;
-  // what the closed-loop kernel does not carry: per-env counters, constraint rows, per-env parameters, run-time compiled
-  // models / expressions, and every integrator but the two fixed-step schemes
-  const int ls = lean_scheme(p->integrator_id);
-  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
-  const PolFn fn = kernels(p->kid).roll_policy[ls];
-  if (!fn) return PCG_E_UNSUPPORTED;
-  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
-  if (T < 1 || t0 < 0 || (int64_t)t0 + (int64_t)T > 0x7fffffffLL) return PCG_E_VALUE;
-  if (io->B == 0) return PCG_OK;
-  if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
-  if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
-  if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
-  if ((a_seq_out && a_comp_stride < io->B) || (obs_seq && obs_comp_stride < io->B)) return PCG_E_DIM;
-  a.t_scalar = t0; a.seed = seed; a.T = T;
-  a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
-  a.obs_seq = obs_seq; a.rew_seq = rew_seq;
-  a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride; a.r_ss = rew_step_stride;
+  PolFn fn;
+  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_policy, &a, &fn));
   PolicyArgs pa;
   pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
   pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
   pa.record_next = record_next_action ? 1 : 0;
-  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, pa);
-  return (int)hipGetLastError();
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, stream);
 }
 
 // ---- ... with a Gaussian actor and an optional critic (pcg_rollout_actor.hpp) -------------------------------------------
@@ -1723,16 +1759,9 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
                       int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
                       int32_t record_next_action, uint64_t seed, void* stream) {
   StepArgs a;
-  int rc = fill_args(p, io, &a);
-  if (rc != PCG_OK) return rc;
-  if (!q) return PCG_E_NULL;
-  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  ActFn fn;
+  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_actor, &a, &fn));
   const DevConst& c = p->hc;
-  const int ls = lean_scheme(p->integrator_id);  // (the plans pcg_rollout_policy takes, asked in its order)
-  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
-  const ActFn fn = kernels(p->kid).roll_actor[ls];
-  if (!fn) return PCG_E_UNSUPPORTED;
-  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
   if (v) {
     if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
     if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
@@ -1743,17 +1772,6 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
   if (!sigma) return PCG_E_NULL;
   for (int i = 0; i < c.na; ++i)
     if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
-  if (T < 1 || t0 < 0 || (int64_t)t0 + (int64_t)T > 0x7fffffffLL) return PCG_E_VALUE;
-  if (io->B == 0) return PCG_OK;
-  if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
-  if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
-  if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
-  if ((a_seq_out && a_comp_stride < io->B) || (u_seq_out && u_comp_stride < io->B) || (obs_seq && obs_comp_stride < io->B))
-    return PCG_E_DIM;
-  a.t_scalar = t0; a.seed = seed; a.T = T;
-  a.d = nullptr;
-  a.obs_seq = obs_seq; a.rew_seq = rew_seq;
-  a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride; a.r_ss = rew_step_stride;
   ActorArgs aa;
   std::memset(&aa, 0, sizeof(aa));
   aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
@@ -1765,8 +1783,8 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
   for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
   aa.c0 = pcg_actor_logp_const(sigma, c.na);
   aa.record_next = record_next_action ? 1 : 0;
-  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, aa);
-  return (int)hipGetLastError();
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, stream);
 }
 
 int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {

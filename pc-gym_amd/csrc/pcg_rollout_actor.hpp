@@ -3,7 +3,8 @@
 // state-independent log_std plus a separate value network; per step the trainer needs the sampled action, its
 // log-probability and the value estimate, and a bootstrap value for the observation after the last step.
 //
-// rollout_policy_kernel's loop (pcg_rollout_policy.hpp), one env per lane, with this between two steps:
+// rollout_policy_kernel's loop (pcg_rollout_policy.hpp, which also says why it is stated twice), one env per lane, with this
+// between two steps:
 //   mu    = actor's last-layer output before its output map                       (policy_raw)
 //   z_i   = rng_normal2(seed, env_offset + e, t, RNG_POLICY + (i >> 1))           (t = t0 + s, the step's shared counter)
 //   u_i   = fma(sigma_i, z_i, mu_i)                                               the sample the trainer's buffer keeps

@@ -203,8 +203,14 @@ constexpr int policy_nin() {
 }
 
 // Closed-loop fused rollout.  Plans without constraint rows, per-env parameters or user expressions, lock-stepped, RK4 / CV8
-// (checked on the host: pcg_rollout_policy).  Reads io->obs (the observation before step t0), writes what pcg_rollout
-// writes plus the recorded policy outputs.
+// (checked on the host: closed_loop_open, pcg_abi.hip).  Reads io->obs (the observation before step t0), writes what
+// pcg_rollout writes plus the recorded policy outputs.
+// The loop is stated here and again in rollout_actor_kernel (pcg_rollout_actor.hpp), ON MEASUREMENT.  As one PCG_DEV
+// function template that both __global__ functions call, with what happens between two steps as a template argument, it
+// returns the same bits but compiles to other code, up to 21 % slower (the affine model's actor kernels; the cstr's 1-2 %);
+// even a helper for the record loops alone cost the cstr's actor 2 %.  Moving a kernel's unchanged body into such a function
+// is enough to change the code, which is consistent with the by-value kernel arguments being read through references in a
+// callee that is optimised before it is inlined.  profiles/r9/closed_loop_refactor.txt, DESIGN.md section 3.6.
 // Waves per SIMD asked of the register allocator for the models of up to ten states (the first hidden layer alone is 128
 // registers; measured on the cstr, tools/policy_rollout_bench.py: profiles/r7/policy_rollout.txt)
 #ifndef PCG_POL_WPE

@@ -30,6 +30,10 @@ def _torch():
     return torch
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 class VecEnv:
     """B environments of one configuration on one GPU.
 
@@ -304,6 +308,12 @@ class VecEnv:
         self.t += T
         return obs_seq, rew_seq
 
+    def _seq_buffers(self, *shape_wanted):
+        """the recorded sequences of a fused closed-loop rollout: one float64 device tensor per (shape, wanted), None where not"""
+        torch = _torch()
+        return [torch.empty(shape, dtype=torch.float64, device=self.device) if wanted else None
+                for shape, wanted in shape_wanted]
+
     def rollout_policy(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
                        record_next_action=False):
         """Fused CLOSED-loop rollout: T steps in one launch, ``policy`` (an :class:`~pcgym_amd.policy.MLPPolicy`)
@@ -312,20 +322,16 @@ class VecEnv:
         as the caller would have passed them to step(); with ``record_next_action`` row T is the policy's proposal for
         the observation after the last step, not applied.  Plans the kernel does not take (constraints, per-env
         parameters, user models, integrators other than rk4 / cv8) raise PcgError: loop over step() for those."""
-        torch = _torch()
         if self.per_env_t:
             raise ValueError("rollout_policy() is lock-stepped only")
-        s, f64, dev, B = self.spec, torch.float64, self.device, self.B
-        T = int(T)
-        a_seq = torch.empty((T + (1 if record_next_action else 0), s.na, B), dtype=f64, device=dev) if collect_actions else None
-        obs_seq = torch.empty((T, s.nobs, B), dtype=f64, device=dev) if collect_obs else None
-        rew_seq = torch.empty((T, B), dtype=f64, device=dev) if collect_rew else None
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
         self._buf.d = None
         _lib.check(self._lib.pcg_rollout_policy(
             self._plan, self._bufp, policy.handle(dev), self.t, T,
-            a_seq.data_ptr() if collect_actions else None, s.na * B, B,
-            obs_seq.data_ptr() if collect_obs else None, s.nobs * B, B,
-            rew_seq.data_ptr() if collect_rew else None, B,
+            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
             int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_policy")
         self.t += T
         return a_seq, obs_seq, rew_seq
@@ -339,26 +345,19 @@ class VecEnv:
         None without a critic): "a" / "u" (T [+1], na, B), "logp" / "val" (T [+1], B), "obs" (T, Nobs, B), "rew" (T, B).  With
         ``record_next_action`` row T holds the four quantities for the observation after the last step (drawn at counter
         t + T, not applied): its value is the bootstrap value.  Plans / networks the kernel does not take raise PcgError."""
-        torch = _torch()
         if self.per_env_t:
             raise ValueError("rollout_actor() is lock-stepped only")
-        s, f64, dev, B = self.spec, torch.float64, self.device, self.B
-        T = int(T)
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
         R = T + (1 if record_next_action else 0)
-        collect_values = collect_values and ac.critic is not None
-        a_seq = torch.empty((R, s.na, B), dtype=f64, device=dev) if collect_actions else None
-        u_seq = torch.empty((R, s.na, B), dtype=f64, device=dev) if collect_samples else None
-        lp = torch.empty((R, B), dtype=f64, device=dev) if collect_logp else None
-        val = torch.empty((R, B), dtype=f64, device=dev) if collect_values else None
-        obs_seq = torch.empty((T, s.nobs, B), dtype=f64, device=dev) if collect_obs else None
-        rew_seq = torch.empty((T, B), dtype=f64, device=dev) if collect_rew else None
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
+            ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
         self._buf.d = None
         _lib.check(self._lib.pcg_rollout_actor(
             self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
             ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
-            ptr(a_seq), s.na * B, B, ptr(u_seq), s.na * B, B, ptr(lp), B, ptr(val), B,
-            ptr(obs_seq), s.nobs * B, B, ptr(rew_seq), B,
+            _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
+            _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
             int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_actor")
         self.t += T
         return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}

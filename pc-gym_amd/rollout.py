@@ -20,6 +20,7 @@ for the whole episode with the policy evaluated in the kernel (``pcg_rollout_pol
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -55,12 +56,26 @@ def _denorm_(t, hm, dim):
     return torch.addcmul(mid, t, half, out=t)
 
 
+@contextlib.contextmanager
+def _recording(env):
+    """a per-step loop that binds each step's observation / reward rows to trajectory storage (``env.bind_outputs``): on the
+    way out, however the loop ends, the env gets its own storage back, holding its latest outputs"""
+    saved = (env.obs_soa, env.rew)
+    try:
+        yield
+    finally:
+        last_o, last_r = env.obs_soa, env.rew
+        env.bind_outputs(*saved)
+        env.obs_soa.copy_(last_o)  # the env keeps its own storage; its latest outputs stay readable there
+        env.rew.copy_(last_r)
+
+
 def collect_rollouts(env, policy=None, actions=None):
     """Roll all B envs of a VecEnv through one episode (N-1 steps) and return the reference-shaped dict.
 
     policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop); an ``MLPPolicy`` is evaluated inside
-              the fused rollout kernel when the plan qualifies (``fused_ok`` below, RK4 / CV8, no per-env parameters, no
-              user model) and like any other callable otherwise, or
+              the fused rollout kernel when the plan qualifies (``fused_policy_ok``: RK4 / CV8, no constraint rows, no
+              per-env parameters, no user model) and like any other callable otherwise, or
     actions : (N, na, B) tensor of policy outputs (open loop; row N-1 is only recorded in ``u``).
 
     Recording is zero-copy: each step's kernel writes its observation / reward rows straight into the trajectory
@@ -108,7 +123,7 @@ def collect_rollouts(env, policy=None, actions=None):
         env.t += N - 1
         u = a if a_hm is None else _denorm_(a.clone(), a_hm, 1)  # never scale the caller's tensor in place
         return {"r": r, "x": _denorm_(x, o_hm, 0), "u": u.permute(1, 0, 2)}
-    if policy is not None and fused_ok and fused_policy_ok(s, policy):
+    if policy is not None and fused_policy_ok(s, policy):
         # closed loop in one launch: the kernel evaluates the policy between two steps and writes observations, policy
         # outputs (column N-1: the action proposed for the final observation) and rewards in the reference's axis order
         x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
@@ -126,8 +141,7 @@ def collect_rollouts(env, policy=None, actions=None):
     us = torch.empty((N, s.na, B), dtype=f64, device=dev)
     xs[0] = env.obs_soa
     rs = r[0]
-    saved = (env.obs_soa, env.rew)
-    try:
+    with _recording(env):
         for i in range(N - 1):
             a = actions[i] if actions is not None else policy(obs)
             a = env._as_soa(a, s.na, "action")
@@ -142,11 +156,6 @@ def collect_rollouts(env, policy=None, actions=None):
             us[N - 1] = env._as_soa(policy(obs), s.na, "action")
         else:
             us[N - 1] = actions[N - 1]
-    finally:
-        last_o, last_r = env.obs_soa, env.rew
-        env.bind_outputs(*saved)
-        env.obs_soa.copy_(last_o)  # the env keeps its own storage; its latest outputs stay readable there
-        env.rew.copy_(last_r)
     out = {"r": r, "x": _denorm_(xs, o_hm, 1).permute(1, 0, 2), "u": _denorm_(us, a_hm, 1).permute(1, 0, 2)}
     if g is not None:
         out["g"] = g
@@ -222,9 +231,8 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
         env.t += T
         act = u[:T]
     else:
-        saved = (env.obs_soa, env.rew)
         z = torch.empty((s.na, B), dtype=f64, device=dev)
-        try:
+        with _recording(env):
             for i in range(T):
                 env.policy_noise(i, out=z)
                 zt = z.t()
@@ -235,11 +243,6 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
                 env.bind_outputs(obs[i + 1], rew[i])
                 o, _, _, _, _ = env.step(ac.action(u))
             val[T] = ac.value(o)
-        finally:
-            last_o, last_r = env.obs_soa, env.rew
-            env.bind_outputs(*saved)
-            env.obs_soa.copy_(last_o)
-            env.rew.copy_(last_r)
     adv, ret = gae(rew, val, gamma, lam, bootstrap_last)
     return {"obs": obs, "act": act, "logp": logp[:T], "val": val, "rew": rew, "adv": adv, "ret": ret}
 

@@ -245,3 +245,189 @@ def feat_params(model, fs):
         p.update(a_delta=True, a_0=(a_lo + a_hi) / 2, a_space_act={"low": a_lo, "high": a_hi},
                  a_space={"low": -(a_hi - a_lo) / 20, "high": (a_hi - a_lo) / 20}, normalise_a=True)
     return p, dict(kw), viol
+
+
+# ---- the closed-loop fused rollouts (tests/test_gpu_policy_rollout.py, tests/test_gpu_actor_rollout.py) ----------------------
+LD = np.longdouble
+U = 2.0 ** -53
+SHAPES = {"affine": (), "1x16": (16,), "2x64": (64, 64)}
+PRE_MAX = 24.0  # the tanh grid covers [-24, 24] (tanh rounds to 1 from 19.1 on); every case asserts its pre-activations lie inside
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+def _record(file_name, line):
+    """print a measured figure and, when PCG_RECORD_DIR names a directory, append it to `file_name` there"""
+    print(line)
+    out = os.environ.get("PCG_RECORD_DIR")
+    if out:
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, file_name), "a") as f:
+            f.write(line + "\n")
+
+
+def _launched(lib, what):
+    """whether a kernel whose name contains `what` was launched since the launch record was last reset"""
+    import ctypes as C
+
+    n = lib.pcg_coverage_names(None, 0, 0)
+    if n <= 1:
+        return False
+    buf = C.create_string_buffer(int(n))
+    lib.pcg_coverage_names(buf, n, 0)
+    return what in buf.value.decode()
+
+
+def _make(p, B, **kw):
+    from pcgym_amd import VecEnv
+
+    return VecEnv(copy.deepcopy(p), n_envs=B, **kw)
+
+
+def make_policy(spec, obs0, hidden, seed):
+    """Fixed-seed weights, scaled by the plan's own boxes so that the units are not saturated and a fair share of the outputs
+    lies strictly inside the clip box: the first layer divides each input by the size of its observation box (1 when the plan
+    normalises) and is centred on the mean reset observation, the output layer spans about the action box's half width around
+    its middle."""
+    from pcgym_amd import MLPPolicy
+
+    rng = np.random.default_rng(seed)
+    n_in, n_out = spec.nobs, spec.na
+    if spec.normalise_o:
+        s_in = np.ones(n_in)
+    else:
+        s_in = np.maximum(np.maximum(np.abs(spec.o_low), np.abs(spec.o_high)), 1e-3)
+    centre = np.mean(obs0, axis=1)
+    if spec.normalise_a:
+        lo, hi = -np.ones(n_out), np.ones(n_out)
+    else:
+        lo, hi = np.asarray(spec.a_low, dtype=float), np.asarray(spec.a_high, dtype=float)
+    mid, half = (hi + lo) / 2, np.maximum((hi - lo) / 2, 1e-3)
+    dims = [n_in, *hidden, n_out]
+    Ws, bs = [], []
+    for l in range(len(dims) - 1):
+        W = rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])
+        b = 0.2 * rng.standard_normal(dims[l + 1])
+        if l == len(dims) - 2:  # (fed by tanh units, which are bounded, or directly by the observation, which is not)
+            W, b = (0.8 if hidden else 0.3) * half[:, None] * W, mid + 0.3 * half * rng.standard_normal(n_out)
+        if l == 0:
+            W = W / s_in[None, :]
+            b = b - W @ centre
+        Ws.append(W), bs.append(b)
+    return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=float(lo.min()), out_high=float(hi.max()))
+
+
+def gamma(n):
+    return n * U / (1 - n * U)
+
+
+def host_reference(pol, obs, k_tanh):
+    """obs (n_in, M) float64 -> (policy output in np.longdouble (n_out, M), running error bound of the device's fp64
+    evaluation (n_out, M), largest |pre-activation|).  Per layer the device forms fl(b + sum_i w_i x_i) with one rounding
+    per FMA: |error| <= gamma_{n+1} (|b| + |W| |x|) + |W| (error of x); tanh and the clip are 1-Lipschitz, the device tanh
+    adds k_tanh ulp of its value."""
+    h = obs.astype(LD)
+    E = np.zeros(obs.shape)
+    pre = 0.0
+    L = len(pol.weights)
+    for l, (W, b) in enumerate(zip(pol.weights, pol.biases)):
+        aW = np.abs(W)
+        mag = aW @ (np.abs(h).astype(np.float64) + E) + np.abs(b)[:, None]
+        E = gamma(W.shape[1] + 1) * mag + aW @ E
+        h = W.astype(LD) @ h + b.astype(LD)[:, None]
+        if l < L - 1:
+            pre = max(pre, float(np.max(np.abs(h))))
+            h = np.tanh(h) if pol.activation == "tanh" else np.maximum(h, 0)
+            if pol.activation == "tanh":
+                E = E + k_tanh * 2.0 ** -52 * (np.abs(h).astype(np.float64) + E)
+    if pol.out_map == "clip":
+        h = np.clip(h, LD(pol.out_low), LD(pol.out_high))
+    elif pol.out_map == "tanh":
+        h = np.tanh(h)
+        E = E + k_tanh * 2.0 ** -52 * (np.abs(h).astype(np.float64) + E)
+    return h, E * (1 + 2.0 ** -10), pre  # (the reference's own 64-bit-mantissa round-off: 2^-11 of the fp64 bound)
+
+
+_K = {}
+
+
+def tanh_k():
+    """largest error of the device tanh in ulp, measured THROUGH the kernel: a policy whose single hidden unit is tanh of the
+    first observation and whose output is that unit (every FMA of it is exact), on a dense grid set into io->obs"""
+    if "k" in _K:
+        return _K["k"]
+    torch = _torch()
+    from pcgym_amd import MLPPolicy
+
+    p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
+    p.update(integrator="rk4")
+    grid = np.concatenate([np.linspace(-PRE_MAX, PRE_MAX, (1 << 18) + 1), np.linspace(-1.0, 1.0, (1 << 17) + 1),
+                           np.geomspace(1e-300, 1.0, 4096), -np.geomspace(1e-300, 1.0, 4096)])
+    B = grid.size
+    env = _make(p, B, seed=1)
+    env.reset()
+    n_in = env.spec.nobs
+    W0 = np.zeros((1, n_in))
+    W0[0, 0] = 1.0
+    pol = MLPPolicy([W0, np.ones((1, 1))], [np.zeros(1), np.zeros(1)], activation="tanh", out_map="none")
+    env.obs_soa.zero_()
+    env.obs_soa[0] = torch.as_tensor(grid, device=env.device)
+    a_seq, _, _ = env.rollout_policy(pol, 1, collect_rew=False)
+    torch.cuda.synchronize()
+    got = a_seq[0, 0].cpu().numpy()
+    env.close(), pol.close()
+    want = np.tanh(grid.astype(LD))
+    ulp = np.spacing(np.abs(want.astype(np.float64)))
+    err = np.abs(got.astype(LD) - want).astype(np.float64) / ulp
+    k = float(np.max(err))
+    assert np.isfinite(k) and k <= 16.0, f"device tanh is {k} ulp off on the grid: not a libm-class tanh"
+    _K["k"] = k
+    _record("policy_rollout_test.txt", f"device tanh: max error {k:.3f} ulp over {B} points of [-{PRE_MAX:g}, {PRE_MAX:g}] (allowance in the action check: k + 1)")
+    return k
+
+
+def _case_params(key, integ):
+    if key == "cstr_noise":  # observation noise: the policy sees the noisy observation, Philox keyed (seed, env, t)
+        p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
+        p.update(integrator=integ, noise=True, noise_percentage=0.002)
+        return p
+    if key == "cstr_raw":  # physical observations in, physical actions out (neither box normalised)
+        p = copy.deepcopy(SC.scenarios()["cstr_raw"]["env_params"])
+        p.update(integrator=integ)
+        return p
+    return sweep_params(key, integ, "scen")
+
+
+def _spread_x0(p, pct=0.02):
+    """every env its own initial state (uniform, +- pct of x0): the lanes of a wave do different arithmetic"""
+    p.update(uncertainty_percentages={"x0": [pct] * 24}, distribution="uniform")
+    return p
+
+
+CASE_KEYS = MODEL_KEYS + ["cstr_noise", "cstr_raw"]
+
+
+def _perm_hidden(pol, seed):
+    """the same function with the hidden units in another order (another summation order in every layer after the first)"""
+    from pcgym_amd import MLPPolicy
+
+    rng = np.random.default_rng(seed)
+    Ws, bs = [w.copy() for w in pol.weights], [b.copy() for b in pol.biases]
+    for l in range(pol.n_hidden):
+        perm = rng.permutation(Ws[l].shape[0])
+        Ws[l], bs[l] = Ws[l][perm], bs[l][perm]
+        Ws[l + 1] = Ws[l + 1][:, perm]
+    return MLPPolicy(Ws, bs, activation=pol.activation, out_map=pol.out_map, out_low=pol.out_low, out_high=pol.out_high)
+
+
+# plans neither closed-loop entry point takes: name -> (scenario, env_params changes)
+UNSUPPORTED_PLANS = {
+    "constraints": ("cstr_cons_pen_norm", dict(integrator="rk4")),
+    "per_env_parameters": ("cstr_canonical", dict(integrator="rk4", uncertainty_percentages={"q": 0.03}, distribution="uniform",
+                                                  uncertainty_bounds={"low": np.array([90.0]), "high": np.array([110.0])})),
+    "rodas5": ("me_canonical", dict(integrator="rodas5")),
+}

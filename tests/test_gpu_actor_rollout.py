@@ -20,35 +20,22 @@ Measured figures are printed and, when PCG_RECORD_DIR names a directory, appende
 """
 import copy
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import scenarios as SC
-from test_gpu_policy_rollout import (CASE_KEYS, SHAPES, PRE_MAX, _case_params, _make, _perm_hidden, _spread_x0, host_reference,
-                                     make_policy, tanh_k)
+from helpers import (CASE_KEYS, LD, PRE_MAX, SHAPES, U, UNSUPPORTED_PLANS, _case_params, _launched, _make, _perm_hidden, _spread_x0,
+                     _torch, host_reference, make_policy, tanh_k)
+from helpers import _record as _record_to
 
 pytestmark = pytest.mark.gpu
 
-LD = np.longdouble
-U = 2.0 ** -53
 RNG_POLICY = 0x400
 
 
-def _torch():
-    import torch
-
-    return torch
-
-
 def _record(line):
-    print(line)
-    out = os.environ.get("PCG_RECORD_DIR")
-    if out:
-        os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "actor_rollout_test.txt"), "a") as f:
-            f.write(line + "\n")
+    _record_to("actor_rollout_test.txt", line)
 
 
 def z_twin(seed, env_offset, B, na, ts):
@@ -420,7 +407,6 @@ def test_collect_onpolicy_takes_the_fused_call(scen, integ, shape, bootstrap_las
     torch = _torch()
     from oracle import oracle as O
     from pcgym_amd import GaussianActorCritic, collect_onpolicy
-    from test_gpu_flat_rollout import _launched
 
     B = 4096
     p = copy.deepcopy(SC.scenarios()[scen]["env_params"])
@@ -476,10 +462,7 @@ def test_collect_onpolicy_takes_the_fused_call(scen, integ, shape, bootstrap_las
 
 # ---- 6. refusals ---------------------------------------------------------------------------------------------------------------
 UNSUPPORTED = {
-    "constraints": ("cstr_cons_pen_norm", dict(integrator="rk4")),
-    "per_env_parameters": ("cstr_canonical", dict(integrator="rk4", uncertainty_percentages={"q": 0.03}, distribution="uniform",
-                                                  uncertainty_bounds={"low": np.array([90.0]), "high": np.array([110.0])})),
-    "rodas5": ("me_canonical", dict(integrator="rodas5")),
+    **UNSUPPORTED_PLANS,
     "tanh_map": ("cstr_canonical", dict(integrator="rk4")),
     "wrong_size_critic": ("cstr_canonical", dict(integrator="rk4")),
 }
@@ -500,7 +483,6 @@ def test_refusals_launch_nothing_and_collection_still_works(what):
     from oracle import oracle as O
     from pcgym_amd import GaussianActorCritic, MLPPolicy, collect_onpolicy
     from pcgym_amd import _abi as abi
-    from test_gpu_flat_rollout import _launched
 
     scen, over = UNSUPPORTED[what]
     p = copy.deepcopy(SC.scenarios()[scen]["env_params"])

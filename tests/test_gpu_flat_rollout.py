@@ -3,25 +3,17 @@ rolled while its guard trusts the fixed step, the handed-over envs each on a lan
 against what it replaces, policy_evaluation.py:71-130 stepped env by env: bitwise equal to T pcg_step launches and to
 the single-kernel rollout, whatever order the lanes finish in, and within round-off of the oracle's per-env loop."""
 import copy
-import ctypes as C
 import os
 import sys
 
 import numpy as np
 import pytest
 
+from helpers import _launched
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
-
-
-def _launched(lib, what):
-    n = lib.pcg_coverage_names(None, 0, 0)
-    if n <= 1:
-        return False
-    buf = C.create_string_buffer(int(n))
-    lib.pcg_coverage_names(buf, n, 0)
-    return what in buf.value.decode()
 
 
 def _params(extras):

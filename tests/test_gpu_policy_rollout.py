@@ -13,6 +13,7 @@ Every comparison is TEACHER-FORCED, so that the amplification of a closed loop n
   public path     collect_rollouts(env, policy=MLPPolicy) against the per-step path, within 8 x the spread of two per-step runs
                   that differ only in the order of the hidden units (+ 1e-13);
   unsupported     constraint rows / per-env parameters / another integrator: PCG_E_UNSUPPORTED, collect_rollouts still works;
+  bad arguments   both entry points: the status of each refused call and the order of the checks, nothing launched or written;
   stream capture  one call inside torch.cuda.graph, replayed twice, equal to the eager call.
 
 Measured figures are printed and, when PCG_RECORD_DIR names a directory, appended to policy_rollout_test.txt there (the copy
@@ -21,165 +22,20 @@ First run on an MI355X: device tanh 0.846 ulp; action error at most 0.54 x its r
 1.8e-14; fused against per-step 0.95-1.2 x the spread of two per-step runs (3e-14 cstr, 7e-16 four_tank).
 """
 import copy
-import os
 
 import numpy as np
 import pytest
 
 import scenarios as SC
-from helpers import MODEL_KEYS
-from helpers import sweep_params as _params
+from helpers import (CASE_KEYS, LD, PRE_MAX, SHAPES, UNSUPPORTED_PLANS, _case_params, _launched, _make, _perm_hidden, _spread_x0,
+                     _torch, host_reference, make_policy, tanh_k)
+from helpers import _record as _record_to
 
 pytestmark = pytest.mark.gpu
 
-LD = np.longdouble
-U = 2.0 ** -53
-SHAPES = {"affine": (), "1x16": (16,), "2x64": (64, 64)}
-PRE_MAX = 24.0  # the tanh grid covers [-24, 24] (tanh rounds to 1 from 19.1 on); every case asserts its pre-activations lie inside
-
-
-def _torch():
-    import torch
-
-    return torch
-
 
 def _record(line):
-    print(line)
-    out = os.environ.get("PCG_RECORD_DIR")
-    if out:
-        os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "policy_rollout_test.txt"), "a") as f:
-            f.write(line + "\n")
-
-
-def _make(p, B, **kw):
-    from pcgym_amd import VecEnv
-
-    return VecEnv(copy.deepcopy(p), n_envs=B, **kw)
-
-
-def make_policy(spec, obs0, hidden, seed):
-    """Fixed-seed weights, scaled by the plan's own boxes so that the units are not saturated and a fair share of the outputs
-    lies strictly inside the clip box: the first layer divides each input by the size of its observation box (1 when the plan
-    normalises) and is centred on the mean reset observation, the output layer spans about the action box's half width around
-    its middle."""
-    from pcgym_amd import MLPPolicy
-
-    rng = np.random.default_rng(seed)
-    n_in, n_out = spec.nobs, spec.na
-    if spec.normalise_o:
-        s_in = np.ones(n_in)
-    else:
-        s_in = np.maximum(np.maximum(np.abs(spec.o_low), np.abs(spec.o_high)), 1e-3)
-    centre = np.mean(obs0, axis=1)
-    if spec.normalise_a:
-        lo, hi = -np.ones(n_out), np.ones(n_out)
-    else:
-        lo, hi = np.asarray(spec.a_low, dtype=float), np.asarray(spec.a_high, dtype=float)
-    mid, half = (hi + lo) / 2, np.maximum((hi - lo) / 2, 1e-3)
-    dims = [n_in, *hidden, n_out]
-    Ws, bs = [], []
-    for l in range(len(dims) - 1):
-        W = rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])
-        b = 0.2 * rng.standard_normal(dims[l + 1])
-        if l == len(dims) - 2:  # (fed by tanh units, which are bounded, or directly by the observation, which is not)
-            W, b = (0.8 if hidden else 0.3) * half[:, None] * W, mid + 0.3 * half * rng.standard_normal(n_out)
-        if l == 0:
-            W = W / s_in[None, :]
-            b = b - W @ centre
-        Ws.append(W), bs.append(b)
-    return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=float(lo.min()), out_high=float(hi.max()))
-
-
-def gamma(n):
-    return n * U / (1 - n * U)
-
-
-def host_reference(pol, obs, k_tanh):
-    """obs (n_in, M) float64 -> (policy output in np.longdouble (n_out, M), running error bound of the device's fp64
-    evaluation (n_out, M), largest |pre-activation|).  Per layer the device forms fl(b + sum_i w_i x_i) with one rounding
-    per FMA: |error| <= gamma_{n+1} (|b| + |W| |x|) + |W| (error of x); tanh and the clip are 1-Lipschitz, the device tanh
-    adds k_tanh ulp of its value."""
-    h = obs.astype(LD)
-    E = np.zeros(obs.shape)
-    pre = 0.0
-    L = len(pol.weights)
-    for l, (W, b) in enumerate(zip(pol.weights, pol.biases)):
-        aW = np.abs(W)
-        mag = aW @ (np.abs(h).astype(np.float64) + E) + np.abs(b)[:, None]
-        E = gamma(W.shape[1] + 1) * mag + aW @ E
-        h = W.astype(LD) @ h + b.astype(LD)[:, None]
-        if l < L - 1:
-            pre = max(pre, float(np.max(np.abs(h))))
-            h = np.tanh(h) if pol.activation == "tanh" else np.maximum(h, 0)
-            if pol.activation == "tanh":
-                E = E + k_tanh * 2.0 ** -52 * (np.abs(h).astype(np.float64) + E)
-    if pol.out_map == "clip":
-        h = np.clip(h, LD(pol.out_low), LD(pol.out_high))
-    elif pol.out_map == "tanh":
-        h = np.tanh(h)
-        E = E + k_tanh * 2.0 ** -52 * (np.abs(h).astype(np.float64) + E)
-    return h, E * (1 + 2.0 ** -10), pre  # (the reference's own 64-bit-mantissa round-off: 2^-11 of the fp64 bound)
-
-
-_K = {}
-
-
-def tanh_k():
-    """largest error of the device tanh in ulp, measured THROUGH the kernel: a policy whose single hidden unit is tanh of the
-    first observation and whose output is that unit (every FMA of it is exact), on a dense grid set into io->obs"""
-    if "k" in _K:
-        return _K["k"]
-    torch = _torch()
-    from pcgym_amd import MLPPolicy
-
-    p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
-    p.update(integrator="rk4")
-    grid = np.concatenate([np.linspace(-PRE_MAX, PRE_MAX, (1 << 18) + 1), np.linspace(-1.0, 1.0, (1 << 17) + 1),
-                           np.geomspace(1e-300, 1.0, 4096), -np.geomspace(1e-300, 1.0, 4096)])
-    B = grid.size
-    env = _make(p, B, seed=1)
-    env.reset()
-    n_in = env.spec.nobs
-    W0 = np.zeros((1, n_in))
-    W0[0, 0] = 1.0
-    pol = MLPPolicy([W0, np.ones((1, 1))], [np.zeros(1), np.zeros(1)], activation="tanh", out_map="none")
-    env.obs_soa.zero_()
-    env.obs_soa[0] = torch.as_tensor(grid, device=env.device)
-    a_seq, _, _ = env.rollout_policy(pol, 1, collect_rew=False)
-    torch.cuda.synchronize()
-    got = a_seq[0, 0].cpu().numpy()
-    env.close(), pol.close()
-    want = np.tanh(grid.astype(LD))
-    ulp = np.spacing(np.abs(want.astype(np.float64)))
-    err = np.abs(got.astype(LD) - want).astype(np.float64) / ulp
-    k = float(np.max(err))
-    assert np.isfinite(k) and k <= 16.0, f"device tanh is {k} ulp off on the grid: not a libm-class tanh"
-    _K["k"] = k
-    _record(f"device tanh: max error {k:.3f} ulp over {B} points of [-{PRE_MAX:g}, {PRE_MAX:g}] (allowance in the action check: k + 1)")
-    return k
-
-
-def _case_params(key, integ):
-    if key == "cstr_noise":  # observation noise: the policy sees the noisy observation, Philox keyed (seed, env, t)
-        p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
-        p.update(integrator=integ, noise=True, noise_percentage=0.002)
-        return p
-    if key == "cstr_raw":  # physical observations in, physical actions out (neither box normalised)
-        p = copy.deepcopy(SC.scenarios()["cstr_raw"]["env_params"])
-        p.update(integrator=integ)
-        return p
-    return _params(key, integ, "scen")
-
-
-def _spread_x0(p, pct=0.02):
-    """every env its own initial state (uniform, +- pct of x0): the lanes of a wave do different arithmetic"""
-    p.update(uncertainty_percentages={"x0": [pct] * 24}, distribution="uniform")
-    return p
-
-
-CASE_KEYS = MODEL_KEYS + ["cstr_noise", "cstr_raw"]
+    _record_to("policy_rollout_test.txt", line)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))
@@ -280,19 +136,6 @@ def test_policy_rollout(key, integ, shape):
     pol.close()
 
 
-def _perm_hidden(pol, seed):
-    """the same function with the hidden units in another order (another summation order in every layer after the first)"""
-    from pcgym_amd import MLPPolicy
-
-    rng = np.random.default_rng(seed)
-    Ws, bs = [w.copy() for w in pol.weights], [b.copy() for b in pol.biases]
-    for l in range(pol.n_hidden):
-        perm = rng.permutation(Ws[l].shape[0])
-        Ws[l], bs[l] = Ws[l][perm], bs[l][perm]
-        Ws[l + 1] = Ws[l + 1][:, perm]
-    return MLPPolicy(Ws, bs, activation=pol.activation, out_map=pol.out_map, out_low=pol.out_low, out_high=pol.out_high)
-
-
 def _dist(a, b):
     """largest difference over x / u / r, each relative to max(1, largest entry of the reference array)"""
     d = 0.0
@@ -308,7 +151,6 @@ def test_collect_rollouts_takes_the_fused_call(scen, integ, shape):
     torch = _torch()
     from oracle import oracle as O
     from pcgym_amd import collect_rollouts
-    from test_gpu_flat_rollout import _launched
 
     B = 4096
     p = copy.deepcopy(SC.scenarios()[scen]["env_params"])
@@ -359,12 +201,7 @@ def test_collect_rollouts_takes_the_fused_call(scen, integ, shape):
     pol.close(), pol2.close()
 
 
-UNSUPPORTED = {
-    "constraints": ("cstr_cons_pen_norm", dict(integrator="rk4")),
-    "per_env_parameters": ("cstr_canonical", dict(integrator="rk4", uncertainty_percentages={"q": 0.03}, distribution="uniform",
-                                                  uncertainty_bounds={"low": np.array([90.0]), "high": np.array([110.0])})),
-    "rodas5": ("me_canonical", dict(integrator="rodas5")),
-}
+UNSUPPORTED = UNSUPPORTED_PLANS
 
 
 @pytest.mark.parametrize("what", list(UNSUPPORTED))
@@ -416,6 +253,111 @@ def test_unsupported_plans_are_refused_and_still_collect(what):
     for e in (env, env2, env3):
         e.close()
     pol.close()
+
+
+@pytest.mark.parametrize("entry", ["policy", "actor"])
+def test_bad_arguments_are_refused_before_any_launch(entry):
+    """the argument checks both entry points share, by return code and in their order of precedence (pcg_abi.hip:
+    closed_loop_open, the entry point's own checks, closed_loop_launch).  First a valid call as the positive control; then
+    every bad call returns its code, leaves env.x, env.obs_soa and every output buffer as they were, and launches no
+    closed-loop kernel.  Every call here is refused by host validation: nothing reaches the device."""
+    torch = _torch()
+    import ctypes as C
+
+    from pcgym_amd import MLPPolicy
+    from pcgym_amd import _abi as abi
+
+    B, T, INT_MAX = 256, 2, 2 ** 31 - 1
+    kernel = f"rollout_{entry}_kernel"
+
+    class Case:
+        def __init__(self, scen):
+            p = copy.deepcopy(SC.scenarios()[scen]["env_params"])
+            p.update(integrator="rk4")
+            self.env = env = _make(p, B, seed=2)
+            env.reset()
+            s = self.spec = env.spec
+            shapes = {"a": (T + 1, s.na, B), "obs": (T, s.nobs, B), "rew": (T, B)}
+            if entry == "actor":
+                shapes.update(u=(T + 1, s.na, B), logp=(T + 1, B), val=(T + 1, B))
+            self.bufs = {n: torch.full(shp, -7.0, dtype=torch.float64, device=env.device) for n, shp in shapes.items()}
+            self.x0, self.o0 = env.x.clone(), env.obs_soa.clone()
+
+        def restore(self):
+            self.env.x.copy_(self.x0), self.env.obs_soa.copy_(self.o0)
+            for b in self.bufs.values():
+                b.fill_(-7.0)
+            torch.cuda.synchronize()
+            self.env._lib.pcg_coverage_names(None, 0, 1)
+
+        def call(self, pol_h, critic_h=None, sigma=None, t0=0, T=T, a_cs=B, o_cs=B, u_cs=B):
+            env, s, b = self.env, self.spec, self.bufs
+            if entry == "policy":
+                rc = env._lib.pcg_rollout_policy(env._plan, env._bufp, pol_h, t0, T, b["a"].data_ptr(), s.na * B, a_cs,
+                                                 b["obs"].data_ptr(), s.nobs * B, o_cs, b["rew"].data_ptr(), B, 1, 1, None)
+            else:
+                sg = (C.c_double * len(sigma))(*sigma) if sigma is not None else None
+                rc = env._lib.pcg_rollout_actor(env._plan, env._bufp, pol_h, critic_h, sg, t0, T, b["a"].data_ptr(), s.na * B, a_cs,
+                                                b["u"].data_ptr(), s.na * B, u_cs, b["logp"].data_ptr(), B, b["val"].data_ptr(), B,
+                                                b["obs"].data_ptr(), s.nobs * B, o_cs, b["rew"].data_ptr(), B, 1, 1, None)
+            torch.cuda.synchronize()
+            return rc
+
+        def refused(self, what, want, *args, **kw):
+            rc = self.call(*args, **kw)
+            assert rc == want, f"{what}: status {rc}, not {want}"
+            assert not _launched(self.env._lib, "rollout_policy_kernel") and not _launched(self.env._lib, "rollout_actor_kernel"), \
+                f"{what}: a refused call launched a closed-loop kernel"
+            assert torch.equal(self.env.x, self.x0) and torch.equal(self.env.obs_soa, self.o0), f"{what}: a refused call wrote the env"
+            assert all(bool((b == -7.0).all()) for b in self.bufs.values()), f"{what}: a refused call wrote an output buffer"
+            self.restore()
+
+    ok = Case("cstr_canonical")
+    spec, dev = ok.spec, ok.env.device
+    pol = make_policy(spec, ok.o0.cpu().numpy(), (16,), seed=3)
+    closing = [pol]
+    h, hc, sigma = pol.handle(dev), None, None
+    if entry == "actor":
+        c = make_policy(spec, ok.o0.cpu().numpy(), (16,), seed=103)
+        critic = MLPPolicy(c.weights[:-1] + [c.weights[-1][:1]], c.biases[:-1] + [c.biases[-1][:1]], activation=c.activation, out_map="none")
+        closing += [c, critic]
+        hc, sigma = critic.handle(dev), [0.25] * spec.na
+    good = (h, hc, sigma)
+
+    # ---- positive control: the valid call runs, writes every buffer, and is seen by the launch record ----
+    ok.restore()
+    assert ok.call(*good) == abi.PCG_OK
+    assert _launched(ok.env._lib, kernel), "the valid call launched nothing"
+    assert not torch.equal(ok.env.x, ok.x0) and not torch.equal(ok.env.obs_soa, ok.o0)
+    for n, b in ok.bufs.items():
+        assert bool((b != -7.0).all()), f"the valid call left part of {n} unwritten"
+    ok.restore()
+
+    # ---- the bad calls ----
+    ok.refused("policy handle None", abi.PCG_E_NULL, None, hc, sigma)
+    ok.refused("T = 0", abi.PCG_E_VALUE, *good, T=0)
+    ok.refused("t0 = -1", abi.PCG_E_VALUE, *good, t0=-1)
+    ok.refused("t0 + T past 2^31 - 1", abi.PCG_E_VALUE, *good, t0=INT_MAX - 1, T=2)
+    ok.refused("action component stride B - 1", abi.PCG_E_DIM, *good, a_cs=B - 1)
+    ok.refused("observation component stride B - 1", abi.PCG_E_DIM, *good, o_cs=B - 1)
+    if entry == "actor":
+        ok.refused("sample component stride B - 1", abi.PCG_E_DIM, *good, u_cs=B - 1)
+
+    # ---- precedence ----
+    wrong = MLPPolicy([np.zeros((spec.na, spec.nobs + 1))], [np.zeros(spec.na)])
+    closing.append(wrong)
+    cons = Case("cstr_cons_pen_norm")
+    assert cons.spec.ncon > 0 and (cons.spec.nobs, cons.spec.na) == (spec.nobs, spec.na)
+    cons.restore()
+    cons.refused("wrong-size policy on a plan with constraint rows", abi.PCG_E_UNSUPPORTED, wrong.handle(dev), hc, sigma)
+    ok.refused("wrong-size policy and T = 0", abi.PCG_E_DIM, wrong.handle(dev), hc, sigma, T=0)
+    if entry == "actor":
+        sq = MLPPolicy(pol.weights, pol.biases, activation="tanh", out_map="tanh")
+        closing.append(sq)
+        ok.refused("tanh-mapped actor without sigma", abi.PCG_E_UNSUPPORTED, sq.handle(dev), hc, None)
+    ok.env.close(), cons.env.close()
+    for q in closing:
+        q.close()
 
 
 def test_stream_capture_replays_the_eager_call():
