@@ -466,7 +466,11 @@ PCG_API int pcg_rollout(pcg_plan* plan, const pcg_buffers* io, int32_t t0, int32
 /* pcg_rollout with explicit element strides (step, component) for the three sequences; the env index is
  * unit-stride.  Lets the collector write straight into the reference's axis order
  * x (Nx, N, reps), u (Nu, N, reps), r (1, N, reps)  (policy_evaluation.py:155-197):
- * obs_comp_stride = N*B, obs_step_stride = B.  Strides must keep rows 16-byte aligned for the 2-env/lane path. */
+ * obs_comp_stride = N*B, obs_step_stride = B.  Strides must keep rows 16-byte aligned for the 2-env/lane path.
+ * PCG_E_DIM for a layout whose rows would overlap: a_comp_stride or obs_comp_stride < B, rew_step_stride < B (T > 1),
+ * or observation rows that are neither step-major (obs_step_stride >= (Nobs-1) obs_comp_stride + B) nor
+ * component-major (obs_step_stride >= B and obs_comp_stride >= (T-1) obs_step_stride + B).  a_seq is only read:
+ * its step stride is free (0 holds one action row for all T steps). */
 PCG_API int pcg_rollout_strided(pcg_plan* plan, const pcg_buffers* io, int32_t t0, int32_t T, const double* a_seq,
                                 int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
                                 int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,

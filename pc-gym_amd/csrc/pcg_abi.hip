@@ -1517,6 +1517,15 @@ int pcg_rollout_strided(pcg_plan* p, const pcg_buffers* io, int32_t t0, int32_t 
   a.o_ss = obs_step_stride; a.o_cs = obs_comp_stride;
   a.r_ss = rew_step_stride;
   if (a.a_cs < io->B || (obs_seq && a.o_cs < io->B)) return PCG_E_DIM;
+  // the rows a rollout WRITES must not overlap (lanes store them without waiting for one another): reward rows a full
+  // batch apart, observation rows either step-major ([T][Nobs][B]-like) or component-major (the reference's axis order)
+  if (rew_seq && T > 1 && a.r_ss < io->B) return PCG_E_DIM;
+  if (obs_seq) {
+    const int64_t B = io->B, n = c.nobs;
+    const bool step_major = T == 1 || a.o_ss >= (n - 1) * a.o_cs + B;
+    const bool comp_major = a.o_ss >= B && (n == 1 || a.o_cs >= (int64_t)(T - 1) * a.o_ss + B);
+    if (!step_major && !comp_major) return PCG_E_DIM;
+  }
   const hipStream_t st = (hipStream_t)stream;
   const Kernels& k = kernels(p->kid);
   if (rollout_unc(p, a, st, &rc) || rollout_jit(p, a, st, &rc) || rollout_lean(p, k, a, io, st, &rc)) return rc;

@@ -28,7 +28,8 @@ import pytest
 
 import scenarios as SC
 # (the configurations are shared with tests/test_gpu_tile_walks.py)
-from helpers import DISPATCH, FIXED, FULL, GUARDED, MODEL_KEYS, SCEN
+from helpers import DISPATCH, FIXED, FULL, GUARDED, MODEL_KEYS, ROS, SCEN
+from helpers import _bars, _close, _unc_params  # (shared with tests/test_gpu_rollout_layouts.py)
 from helpers import feat_params as _feat_params
 from helpers import sweep_actions as _actions
 from helpers import sweep_params as _params
@@ -36,25 +37,7 @@ from helpers import worst_rel as _worst
 
 pytestmark = pytest.mark.gpu
 
-ROS = ("rodas3", "rodas4", "rodas5")
 ADAPT = ("dopri5", "tsit5") + ROS
-
-
-def _bars(key, integ):
-    """(largest difference over every lane, share of lanes with the oracle's step sequence) one env step may show.
-    The pow() form of the extraction cascades under an EXPLICIT adaptive pair runs at its stability limit, where the
-    embedded error estimate is round-off amplified ~1e8 x: pow() of libm here and of OCML there differ in the last bit, a
-    few steps later the sequences do, and the results agree to the plan's tolerance (1e-6), not to round-off -- the
-    multiply-only form (eq_exponent == 2, the reference's default) has a bit-identical twin and is held to round-off
-    like every other model (tests/helpers.py "adaptive parity")."""
-    if "^" in key and integ in ("dopri5", "tsit5"):
-        return 5e-6, 0.5
-    if key == "crystallization" and integ in ROS:
-        # moments from 1e-1 to 1e9 in one state vector: the difference-quotient Jacobian's last-bit noise (dJ/J ~ 1e-8)
-        # passes through an LU of that conditioning; measured 1.1e-6 on single lanes of the full action box, identical
-        # step sequences (the plan's tolerance is 1e-6; every other model stays below 5e-8)
-        return 5e-6, 0.98
-    return 1e-6, 0.98
 
 
 def _make(p, B, **kw):
@@ -249,18 +232,6 @@ def test_integrate_sweep(key, integ, lds):
 
 
 # ---- the other entry points of a plan ----------------------------------------------------------------------------------------
-def _close(a, b):
-    import torch
-
-    a, b = a.double(), b.double()
-    fa, fb = torch.isfinite(a), torch.isfinite(b)
-    if not torch.equal(fa, fb):
-        return float("inf")
-    if not fa.any():
-        return 0.0
-    return ((a[fa] - b[fa]).abs() / b[fa].abs().clamp_min(1e-9)).max().item()
-
-
 def _shape_cases():
     out = []
     for key in MODEL_KEYS:
@@ -353,22 +324,6 @@ def test_shape_sweep(key, integ, feat, dispatch):
 
 
 # ---- per-env parameters ------------------------------------------------------------------------------------------------------
-def _unc_params(key, integ):
-    from pcgym_amd.models import get_model
-
-    model = key.partition("^")[0]
-    mi = get_model(model)
-    if mi.affine_builder is not None:
-        pytest.skip("affine registry models have no per-env parameter kernel")
-    names = [k for k, v in mi.parameters.items() if float(v) != 0.0 and k not in ("N", "eq_exponent")]
-    pick = names[:2]
-    p = _params(key, integ, "lean")
-    p.update(uncertainty_percentages={k: 0.03 for k in pick}, distribution="uniform",
-             uncertainty_bounds={"low": np.array([min(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick]),
-                                 "high": np.array([max(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick])})
-    return p
-
-
 @pytest.mark.parametrize("pe", [False, True], ids=["lockstep", "per_env_t"])
 @pytest.mark.parametrize("integ", ["rk4", "dopri5"])
 @pytest.mark.parametrize("key", MODEL_KEYS)
