@@ -991,590 +991,6 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
   if (PER_ENV_T) A.t[e] = t + 1;
 }
 
-// ---------------------------------------------------------------------------
-// Streaming variant for the lean, lock-stepped hot path (BASELINE configs[1]):
-//   * persistent grid (all workgroups resident), grid-stride over tiles of 256*EPL envs;
-//   * EPL = 2 environments per lane -> every global access is 16 B per lane (dwordx4),
-//     1 KiB contiguous per wave-instruction, and the two envs give the VALU two
-//     independent dependency chains through exp/div;
-//   * the loads of tile i+1 are issued before tile i is integrated, so each wave has HBM
-//     reads in flight while it computes, and waves drift out of phase instead of
-//     alternating chip-wide "all load / all compute / all store" rounds.
-// Preconditions (checked on the host): no per-env t, no extras, no a_delta, no per-env d,
-// B % EPL == 0 and 16-byte aligned rows when EPL == 2.
-// ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-// Lean env step for W envs per lane (Pack<W>): the hot path of BASELINE configs[1].
-// Same statements as env_step with everything the lean plan cannot contain removed (a_delta,
-// per-env / Gaussian disturbances, noise, constraints, terminal reward); the lock-stepped batch makes
-// the SP / disturbance slots, `done` and all schedule values wave-uniform scalars.
-// ---------------------------------------------------------------------------
-template <int NX, int W>
-PCG_DEV Pack<W> pick(const Pack<W> (&v)[NX], int idx) {
-  Pack<W> r(0.0);
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-#pragma unroll
-    for (int j = 0; j < W; ++j) r.v[j] = (i == idx) ? v[i].v[j] : r.v[j];
-  return r;
-}
-
-template <class M, int W>
-struct LeanOut {
-  Pack<W> ox[M::NX];
-  Pack<W> rew;
-  bool done;                // wave-uniform
-};
-
-// INTEG: PCG_INT_RK4 (the lean kernels' scheme) or PCG_INT_CV8.  (A guarded scheme with the adaptive fallback inside this
-// kernel was built and measured: 41.3 us against 37 us in the general kernel on the canonical cstr loop -- the fallback's
-// registers leave one env per lane at four waves per SIMD -- and 26 % slower when half the batch escalates, because a
-// 256-thread workgroup then waits for its slowest env.)
-// Round 4: the kernel's time follows its vector-instruction count (profiles/r4/headline_bisect.txt: +8 % instructions,
-// +9 % time), so everything wave-uniform is gone from the vector unit -- the SP / disturbance slots of step t come
-// finished from the host (LeanStep, scalar loads), h/2 and h/6 too, and the normalised-action branch is a scalar branch
-// instead of both values and a select.
-template <class M, int W, int INTEG = PCG_INT_RK4>
-PCG_DEV void env_step_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, int t,
-                           const Pack<W> (&a_in)[M::NA], Pack<W> (&x)[M::NX], LeanOut<M, W>& out) {
-  constexpr int NX = M::NX, NA = M::NA, NDM = M::NDM;
-  using R = Pack<W>;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
-  const int N = c.N, nsp = c.nsp;
-  typename M::CKP& kp = model_kp<M>(c);
-  // action map (pcgym.py:371-375) and held disturbance inputs (pcgym.py:386-404)
-  R u[NA + NDM];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) u[i] = (i < na) ? a_in[i] : R(0.0);
-  if (c.flags & PCG_F_NORMALISE_A) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-      if (i < na) u[i] = action_map(a_in[i], c.a_lo[i], c.a_hi[i], true, false);
-    asm volatile("");  // keep it a (scalar) branch
-  }
-#pragma unroll
-  for (int j = 0; j < NDM; ++j) u[NA + j] = R(L.ud[j]);
-  // integrate over [0,dt] with the input held (integrator.py:163-182)
-  const typename M::template HoldT<R> hold = M::template hold<R>(kp, u);
-  const RhsFn<M, R> f{kp, hold};
-  if constexpr (INTEG == PCG_INT_CV8) {
-    cv8<NX>(f, x, c.h, c.substeps);
-  } else {
-    rk4<NX>(f, x, c.h, c.h2, c.h6, c.substeps);
-  }
-  // reward against SP[t_new] (pcgym.py:535-558)
-  R r(0.0);
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nsp) {
-      const R dd = pick<NX, W>(x, c.sp_index[k]) - L.spn[k];
-      r = r + (-(dd * dd)) * c.r_scale[k];
-    }
-  out.rew = r;
-  out.done = (t + 1 == N - 1);  // pcgym.py:448-449
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-    if (i < nx) out.ox[i] = (x[i] - c.omap[i].lo) * c.omap[i].sc + c.omap[i].off;
-}
-
-template <int EPL>
-struct Vec;
-template <>
-struct Vec<1> {
-  using T = double;
-  PCG_DEV static double get(const T& v, int) { return v; }
-  PCG_DEV static T make(const double (&s)[1]) { return s[0]; }
-  // streaming store: the data is not re-read by this kernel (obs / reward go to the policy)
-  PCG_DEV static void store_nt(double* p, const double (&s)[1]) { __builtin_nontemporal_store(s[0], p); }
-  PCG_DEV static T load_nt(const double* p) { return __builtin_nontemporal_load(p); }
-};
-template <>
-struct Vec<2> {
-  using T = double2;
-  typedef double d2 __attribute__((ext_vector_type(2)));
-  PCG_DEV static double get(const T& v, int j) { return j ? v.y : v.x; }
-  PCG_DEV static T make(const double (&s)[2]) { return make_double2(s[0], s[1]); }
-  PCG_DEV static void store_nt(double* p, const double (&s)[2]) {
-    __builtin_nontemporal_store(d2{s[0], s[1]}, reinterpret_cast<d2*>(p));
-  }
-  PCG_DEV static T load_nt(const double* p) {
-    const d2 v = __builtin_nontemporal_load(reinterpret_cast<const d2*>(p));
-    return make_double2(v.x, v.y);
-  }
-};
-
-PCG_DEV void land(double& v) { asm volatile("" : "+v"(v)); }
-PCG_DEV void land(double2& v) {
-  asm volatile("" : "+v"(v.x));
-  asm volatile("" : "+v"(v.y));
-}
-
-// stores of one lean tile: the state back in place, observation / reward (non-temporal on request), done flags.
-// Rows are addressed as (uniform row base) + (32-bit byte offset of the lane): the row bases stay in scalar registers and the
-// lane's offset is ONE vector register for every row (the 64-bit per-row addresses of rounds 1-3 were two dozen vector
-// instructions per tile).  Callers guarantee B < 2^28.
-template <class T>
-PCG_DEV T* row_at(double* base, uint32_t off8) {
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off8);
-}
-template <class T>
-PCG_DEV const T* row_at(const double* base, uint32_t off8) {
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off8);
-}
-template <class M, int EPL>
-PCG_DEV void store_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, uint32_t e0,
-                        const Pack<EPL> (&xs)[M::NX], const LeanOut<M, EPL>& out, bool nt) {
-  using V = typename Vec<EPL>::T;
-  constexpr int NX = M::NX;
-  const size_t B = (size_t)A.B;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int nso = c.nsp_obs;
-  const uint32_t o8 = e0 * 8u;
-  double tmp[EPL];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-    if (i < nx) {
-      if (A.nt_stores & 2) Vec<EPL>::store_nt(row_at<double>(A.x + (size_t)i * B, o8), xs[i].v);
-      else *row_at<V>(A.x + (size_t)i * B, o8) = Vec<EPL>::make(xs[i].v);
-      if (nt) Vec<EPL>::store_nt(row_at<double>(A.obs + (size_t)i * B, o8), out.ox[i].v);
-      else *row_at<V>(A.obs + (size_t)i * B, o8) = Vec<EPL>::make(out.ox[i].v);
-    }
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nso) {
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tmp[j] = L.osp[k];
-      if (nt) Vec<EPL>::store_nt(row_at<double>(A.obs + (size_t)(nx + k) * B, o8), tmp);
-      else *row_at<V>(A.obs + (size_t)(nx + k) * B, o8) = Vec<EPL>::make(tmp);
-    }
-#pragma unroll
-  for (int k = 0; k < M::NDM; ++k)
-    if (k < c.nd) {
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tmp[j] = L.od[k];
-      if (nt) Vec<EPL>::store_nt(row_at<double>(A.obs + (size_t)(nx + nso + k) * B, o8), tmp);
-      else *row_at<V>(A.obs + (size_t)(nx + nso + k) * B, o8) = Vec<EPL>::make(tmp);
-    }
-  if (nt) Vec<EPL>::store_nt(row_at<double>(A.rew, o8), out.rew.v);
-  else *row_at<V>(A.rew, o8) = Vec<EPL>::make(out.rew.v);
-  if (EPL == 2) *reinterpret_cast<uint16_t*>(A.done + e0) = out.done ? (uint16_t)0x0101u : (uint16_t)0;
-  else A.done[e0] = out.done ? 1 : 0;
-}
-
-// reset of the EPL consecutive envs of one lean lane (lock-stepped batch, no per-env parameters / a_delta: those
-// configurations never reach the lean kernels): same draws as reset_env, stored 16 bytes per lane and row
-template <class M, int EPL>
-PCG_DEV void reset_lean(const StepArgs& A, CDevConst& c, int64_t e0, uint64_t seed, bool nt) {
-  using V = typename Vec<EPL>::T;
-  constexpr int NX = M::NX;
-  const int64_t B = A.B;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int nso = c.nsp_obs, nd = c.nd;
-  double tmp[EPL], tob[EPL];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-    if (i < nx) {
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) {
-        double v = c.x0[i];
-        if (c.has_x0_unc && c.x0_unc[i] != 0.0) {  // apply_uncertainties, pcgym.py:255-261
-          const uint64_t env_id = (uint64_t)(A.env_offset + e0 + j);
-          const double pct = c.x0_unc[i];
-          if (c.flags & PCG_F_X0_NORMAL) {
-            double z0, z1;
-            rng_normal2(seed, env_id, 0u, RNG_RESET + (uint32_t)(i >> 1), z0, z1);
-            v = c.x0[i] + pct * c.x0[i] * ((i & 1) ? z1 : z0);
-          } else {
-            double u0, u1;
-            rng_uniform2(seed, env_id, 0u, RNG_RESET + (uint32_t)(i >> 1), u0, u1);
-            v = c.x0[i] * (1 + pct * (2.0 * ((i & 1) ? u1 : u0) - 1.0));
-          }
-        }
-        tmp[j] = v;
-        tob[j] = (v - c.omap[i].lo) * c.omap[i].sc + c.omap[i].off;
-      }
-      *reinterpret_cast<V*>(A.x + (size_t)i * B + e0) = Vec<EPL>::make(tmp);
-      if (nt) Vec<EPL>::store_nt(A.obs + (size_t)i * B + e0, tob);
-      else *reinterpret_cast<V*>(A.obs + (size_t)i * B + e0) = Vec<EPL>::make(tob);
-    }
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nso) {
-      const double o = (c.x0[nx + k] - c.omap[nx + k].lo) * c.omap[nx + k].sc + c.omap[nx + k].off;
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tob[j] = o;
-      if (nt) Vec<EPL>::store_nt(A.obs + (size_t)(nx + k) * B + e0, tob);
-      else *reinterpret_cast<V*>(A.obs + (size_t)(nx + k) * B + e0) = Vec<EPL>::make(tob);
-    }
-#pragma unroll
-  for (int k = 0; k < M::NDM; ++k)
-    if (k < nd) {  // disturbances[k][0] (pcgym.py:291-298, quirk Q6)
-      const int q = nx + nso + k;
-      const double o = (A.sched[(size_t)(c.nsp + k) * c.N] - c.omap[q].lo) * c.omap[q].sc + c.omap[q].off;
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tob[j] = o;
-      if (nt) Vec<EPL>::store_nt(A.obs + (size_t)q * B + e0, tob);
-      else *reinterpret_cast<V*>(A.obs + (size_t)q * B + e0) = Vec<EPL>::make(tob);
-    }
-}
-
-template <class M, int INTEG, int EPL, int UNR>
-__global__ __launch_bounds__(BLOCK, (PCG_LEAN_WPE > wpe(M::NX, INTEG, false) ? PCG_LEAN_WPE : wpe(M::NX, INTEG, false)))
-void step_kernel_stream(const StepArgs A) {
-  // One workgroup = UNR sub-tiles of 256*EPL envs.  All UNR sub-tiles' inputs are requested up front
-  // (UNR * (NX+NA) loads in flight per lane), then the sub-tiles are integrated and stored one after
-  // the other: the memory system works on sub-tile u+1.. while the VALU integrates sub-tile u, and
-  // results leave as soon as each sub-tile is done instead of in one burst per wave.
-  CDevConst& c = *A.C;
-  constexpr int NX = M::NX, NA = M::NA;
-  using V = typename Vec<EPL>::T;
-  const int64_t B = A.B;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
-  const int nso = c.nsp_obs;
-  const int t = A.t_scalar;
-  const bool nt = (A.nt_stores & 1) != 0;
-  constexpr int64_t SUB = (int64_t)BLOCK * EPL;  // envs per sub-tile
-  const int64_t tile = SUB * UNR;
-  const int64_t ntile = (B + tile - 1) / tile;
-  for (int64_t it = blockIdx.x; it < ntile; it += gridDim.x) {
-    V xv[UNR][NX], av[UNR][NA];
-    bool live[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int64_t e0 = it * tile + u * SUB + (int64_t)threadIdx.x * EPL;
-      live[u] = e0 < B;
-      if (live[u]) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-          if (i < nx) xv[u][i] = *reinterpret_cast<const V*>(A.x + (size_t)i * B + e0);
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-          if (i < na) av[u][i] = *reinterpret_cast<const V*>(A.a + (size_t)i * B + e0);
-      }
-    }
-    // Land ALL inputs here, while only loads are outstanding.  gfx9-class hardware counts loads and
-    // stores in one counter (vmcnt) and lets the two kinds complete out of order, so once a store is
-    // pending the compiler can only wait with vmcnt(0) -- i.e. every later "wait for my input" would
-    // also wait for the previous sub-tile's stores to be acknowledged (microseconds under load).
-    // Passing the loaded registers through an empty asm makes this the single wait of the tile:
-    // after it, the sub-tiles are integrated and stored back-to-back and no store is ever waited for.
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-#pragma unroll
-      for (int i = 0; i < NX; ++i) land(xv[u][i]);
-#pragma unroll
-      for (int i = 0; i < NA; ++i) land(av[u][i]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int64_t e0 = it * tile + u * SUB + (int64_t)threadIdx.x * EPL;
-      if (!live[u]) continue;
-      if constexpr (INTEG == PCG_INT_RK4) {
-        // W = EPL envs advance together through one instruction stream (independent chains -> ILP)
-        Pack<EPL> xs[NX], as[NA];
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) xs[i].v[j] = (i < nx) ? Vec<EPL>::get(xv[u][i], j) : 0.0;
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) as[i].v[j] = (i < na) ? Vec<EPL>::get(av[u][i], j) : 0.0;
-        LeanOut<M, EPL> out;
-        env_step_lean<M, EPL>(A, c, A.lean[min(t, c.N - 1)], t, as, xs, out);
-        store_lean<M, EPL>(A, c, A.lean[min(t, c.N - 1)], (uint32_t)e0, xs, out, nt);
-      } else {
-      EnvOut<M> out[EPL];
-      double xs[EPL][NX];
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) {
-        double a[NA];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xs[j][i] = (i < nx) ? Vec<EPL>::get(xv[u][i], j) : 0.0;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) a[i] = (i < na) ? Vec<EPL>::get(av[u][i], j) : 0.0;
-        env_step<M, INTEG, false, false, false>(A, c, nullptr, nullptr, e0 + j, t, a, xs[j], out[j]);
-      }
-      double tmp[EPL];
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-        if (i < nx) {
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = xs[j][i];
-          *reinterpret_cast<V*>(A.x + (size_t)i * B + e0) = Vec<EPL>::make(tmp);
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = out[j].ox[i];
-          if (nt) Vec<EPL>::store_nt(A.obs + (size_t)i * B + e0, tmp);
-          else *reinterpret_cast<V*>(A.obs + (size_t)i * B + e0) = Vec<EPL>::make(tmp);
-        }
-#pragma unroll
-      for (int k = 0; k < PCG_MAX_NSP; ++k)
-        if (k < nso) {
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = out[j].osp[k];
-          if (nt) Vec<EPL>::store_nt(A.obs + (size_t)(nx + k) * B + e0, tmp);
-          else *reinterpret_cast<V*>(A.obs + (size_t)(nx + k) * B + e0) = Vec<EPL>::make(tmp);
-        }
-#pragma unroll
-      for (int k = 0; k < M::NDM; ++k)
-        if (k < c.nd) {
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = out[j].od[k];
-          if (nt) Vec<EPL>::store_nt(A.obs + (size_t)(nx + nso + k) * B + e0, tmp);
-          else *reinterpret_cast<V*>(A.obs + (size_t)(nx + nso + k) * B + e0) = Vec<EPL>::make(tmp);
-        }
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tmp[j] = out[j].rew;
-      if (nt) Vec<EPL>::store_nt(A.rew + e0, tmp);
-      else *reinterpret_cast<V*>(A.rew + e0) = Vec<EPL>::make(tmp);
-      if (EPL == 2) {
-        *reinterpret_cast<uint16_t*>(A.done + e0) =
-            (uint16_t)((out[0].done ? 1u : 0u) | (out[EPL - 1].done ? 0x100u : 0u));
-      } else {
-        A.done[e0] = out[0].done ? 1 : 0;
-      }
-      }  // INTEG
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Software-pipelined persistent variant of the lean kernel (PCG_OPT_VARIANT 4): each wave walks
-// over its tiles and always has the NEXT tile's inputs in flight while it integrates the current one.
-//   loop:  land(cur)            -- the only wait: cur's loads (issued one iteration ago) + previous stores
-//          issue loads(next)
-//          integrate(cur)       -- no memory operation inside the lean step
-//          issue stores(cur)    -- never waited for explicitly
-// The `land` placement matters: loads and stores share one in-order-per-kind counter (vmcnt), so the
-// compiler can only wait with vmcnt(0) once stores are pending; waiting BEFORE the prefetch is issued
-// keeps the prefetch out of that wait.
-// ---------------------------------------------------------------------------
-// AR: the instantiation launched for the LAST step of a lock-stepped episode with same-launch auto-reset
-// (pcg_step_autoreset).  It is a separate instantiation because the inlined reset path (Philox draws for the x0 /
-// parameter uncertainty) raises the register count of the whole kernel from 75 to 118 (6 -> 4 waves per SIMD);
-// the other N-2 steps of the episode run the lean one.
-template <class M, int EPL, bool AR = false, int INTEG = PCG_INT_RK4>
-__global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) void step_kernel_pipe(const StepArgs A) {
-  CDevConst& c = *A.C;
-  constexpr int NX = M::NX, NA = M::NA;
-  using V = typename Vec<EPL>::T;
-  const uint32_t B = (uint32_t)A.B;  // < 2^28 (step_impl): 32-bit env indices and byte offsets, row bases in scalar registers
-  const size_t Bs = (size_t)A.B;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
-  const int t = A.t_scalar;
-  const PCG_CONSTANT LeanStep& L = A.lean[min(t, c.N - 1)];
-  const bool nt = (A.nt_stores & 1) != 0;
-  const bool ntl = (A.nt_stores & 4) != 0;
-  constexpr uint32_t TILE = (uint32_t)BLOCK * EPL;
-  const uint32_t ntile = (B + TILE - 1) / TILE;
-  uint32_t it = blockIdx.x;
-  if (it >= ntile) return;
-  V xv[NX], av[NA];
-  uint32_t e0 = it * TILE + threadIdx.x * EPL;
-  bool live = e0 < B;
-  auto load = [&](uint32_t ee, V (&xd)[NX], V (&ad)[NA]) {
-    const uint32_t o8 = ee * 8u;
-    if (ntl) {
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-        if (i < nx) xd[i] = Vec<EPL>::load_nt(row_at<double>(A.x + (size_t)i * Bs, o8));
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-        if (i < na) ad[i] = Vec<EPL>::load_nt(row_at<double>(A.a + (size_t)i * Bs, o8));
-    } else {
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-        if (i < nx) xd[i] = *row_at<V>(A.x + (size_t)i * Bs, o8);
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-        if (i < na) ad[i] = *row_at<V>(A.a + (size_t)i * Bs, o8);
-    }
-  };
-#ifdef PCG_TIMELINE  // measurement build (tools/timeline_probe.py): per-wave stamps of the 100 MHz wall clock into A.g
-  int tl_it = 0;
-#define PCG_TL(k)                                                                                              \
-  if ((threadIdx.x & 63) == 0 && A.g)                                                                          \
-  reinterpret_cast<unsigned long long*>(A.g)[((size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + tl_it) * 8 + (k)] = \
-      wall_clock64()
-#else
-#define PCG_TL(k)
-#endif
-  PCG_TL(0);
-  if (live) load(e0, xv, av);
-  for (;;) {
-#pragma unroll
-    for (int i = 0; i < NX; ++i) land(xv[i]);
-#pragma unroll
-    for (int i = 0; i < NA; ++i) land(av[i]);
-    PCG_TL(1);
-    const uint32_t itn = it + gridDim.x;
-    const uint32_t e1 = itn * TILE + threadIdx.x * EPL;
-    const bool live_n = (itn < ntile) && (e1 < B);
-    V xn[NX], an[NA];
-    asm volatile("" ::: "memory");
-    if (live_n) load(e1, xn, an);
-    asm volatile("" ::: "memory");
-    if (live) {
-      Pack<EPL> xs[NX], as[NA];
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) xs[i].v[j] = (i < nx) ? Vec<EPL>::get(xv[i], j) : 0.0;
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) as[i].v[j] = (i < na) ? Vec<EPL>::get(av[i], j) : 0.0;
-      LeanOut<M, EPL> out;
-      env_step_lean<M, EPL, INTEG>(A, c, L, t, as, xs, out);
-      PCG_TL(2);
-      if (A.status) {  // per-env health: a fixed step can only leave a non-finite state; only failures are written
-#pragma unroll
-        for (int j = 0; j < EPL; ++j) {
-          bool ok = true;
-#pragma unroll
-          for (int i = 0; i < NX; ++i) ok = ok && (__builtin_fabs(xs[i].v[j]) < __builtin_inf());
-          if (!ok) A.status[e0 + j] = PCG_ST_NONFINITE;
-        }
-      }
-      if (AR && A.auto_reset && out.done) {
-        // last step of a lock-stepped episode with same-launch auto-reset: reward / done of the finished step,
-        // then the new episode's state and observation instead of the terminal ones (pcg_step_autoreset)
-        if (nt) Vec<EPL>::store_nt(A.rew + e0, out.rew.v);
-        else *reinterpret_cast<V*>(A.rew + e0) = Vec<EPL>::make(out.rew.v);
-        if (EPL == 2) *reinterpret_cast<uint16_t*>(A.done + e0) = (uint16_t)0x0101u;
-        else A.done[e0] = 1;
-        reset_lean<M, EPL>(A, c, (int64_t)e0, A.reset_seed, nt);
-      } else {
-        store_lean<M, EPL>(A, c, L, e0, xs, out, nt);
-      }
-    }
-    PCG_TL(3);
-#ifdef PCG_TIMELINE
-    if (itn >= ntile) {
-      __builtin_amdgcn_s_waitcnt(0);  // all stores of this wave acknowledged
-      PCG_TL(4);
-    }
-    tl_it = 1;
-#endif
-    if (itn >= ntile) break;
-    it = itn;
-    e0 = e1;
-    live = live_n;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xv[i] = xn[i];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) av[i] = an[i];
-  }
-}
-
-// Lean fused rollout: T lock-stepped env steps, W envs per lane, state in registers throughout;
-// per step only the action row(s) are read and reward (+ observation rows, if requested) written.
-template <class M, int EPL>
-__global__ __launch_bounds__(BLOCK) void rollout_kernel_lean(const StepArgs A) {
-  CDevConst& c = *A.C;
-  constexpr int NX = M::NX, NA = M::NA;
-  using V = typename Vec<EPL>::T;
-  const int64_t B = A.B;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
-  const int nso = c.nsp_obs, nobs = c.nobs;
-  const int64_t e0 = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * EPL;
-  if (e0 >= B) return;
-  Pack<EPL> xs[NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) {
-    V v;
-    if (i < nx) v = *reinterpret_cast<const V*>(A.x + (size_t)i * B + e0);
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) xs[i].v[j] = (i < nx) ? Vec<EPL>::get(v, j) : 0.0;
-  }
-  V an[NA];
-#pragma unroll
-  for (int i = 0; i < NA; ++i)
-    if (i < na) an[i] = *reinterpret_cast<const V*>(A.a_seq + (size_t)i * A.a_cs + e0);
-  LeanOut<M, EPL> out;
-  for (int s = 0; s < A.T; ++s) {
-    Pack<EPL> as[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      land(an[i]);
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) as[i].v[j] = (i < na) ? Vec<EPL>::get(an[i], j) : 0.0;
-    }
-    asm volatile("" ::: "memory");
-    if (s + 1 < A.T) {  // next step's action in flight during this step's integration
-      const double* nxt = A.a_seq + (size_t)(s + 1) * A.a_ss;
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-        if (i < na) an[i] = *reinterpret_cast<const V*>(nxt + (size_t)i * A.a_cs + e0);
-    }
-    asm volatile("" ::: "memory");
-    const PCG_CONSTANT LeanStep& L = A.lean[min(A.t_scalar + s, c.N - 1)];
-    env_step_lean<M, EPL>(A, c, L, A.t_scalar + s, as, xs, out);
-    if (A.rew_seq) Vec<EPL>::store_nt(A.rew_seq + (size_t)s * A.r_ss + e0, out.rew.v);
-    if (A.obs_seq) {
-      double* o = A.obs_seq + (size_t)s * A.o_ss + e0;
-      const int64_t ocs = A.o_cs;
-      double tmp[EPL];
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-        if (i < nx) Vec<EPL>::store_nt(o + (size_t)i * ocs, out.ox[i].v);
-#pragma unroll
-      for (int k = 0; k < PCG_MAX_NSP; ++k)
-        if (k < nso) {
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = L.osp[k];
-          Vec<EPL>::store_nt(o + (size_t)(nx + k) * ocs, tmp);
-        }
-#pragma unroll
-      for (int k = 0; k < M::NDM; ++k)
-        if (k < c.nd) {
-#pragma unroll
-          for (int j = 0; j < EPL; ++j) tmp[j] = L.od[k];
-          Vec<EPL>::store_nt(o + (size_t)(nx + nso + k) * ocs, tmp);
-        }
-    }
-  }
-  if (A.status) {  // a non-finite state is absorbing: one check at the end covers the T steps (sticky byte)
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i < NX; ++i) ok = ok && (__builtin_fabs(xs[i].v[j]) < __builtin_inf());
-      if (!ok) A.status[e0 + j] = PCG_ST_NONFINITE;
-    }
-  }
-  // final state and the last step's outputs into the regular per-step buffers
-  const PCG_CONSTANT LeanStep& L = A.lean[min(A.t_scalar + A.T - 1, c.N - 1)];
-  double tmp[EPL];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-    if (i < nx) {
-      *reinterpret_cast<V*>(A.x + (size_t)i * B + e0) = Vec<EPL>::make(xs[i].v);
-      *reinterpret_cast<V*>(A.obs + (size_t)i * B + e0) = Vec<EPL>::make(out.ox[i].v);
-    }
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nso) {
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tmp[j] = L.osp[k];
-      *reinterpret_cast<V*>(A.obs + (size_t)(nx + k) * B + e0) = Vec<EPL>::make(tmp);
-    }
-#pragma unroll
-  for (int k = 0; k < M::NDM; ++k)
-    if (k < c.nd) {
-#pragma unroll
-      for (int j = 0; j < EPL; ++j) tmp[j] = L.od[k];
-      *reinterpret_cast<V*>(A.obs + (size_t)(nx + nso + k) * B + e0) = Vec<EPL>::make(tmp);
-    }
-  *reinterpret_cast<V*>(A.rew + e0) = Vec<EPL>::make(out.rew.v);
-  if (EPL == 2) *reinterpret_cast<uint16_t*>(A.done + e0) = out.done ? (uint16_t)0x0101u : (uint16_t)0;
-  else A.done[e0] = out.done ? 1 : 0;
-}
-
 // Open-loop fused rollout: T env steps with x in registers ("next" row f-1).
 // UNC: per-env uncertain parameters (p_unc, sampled by the reset that precedes the episode: pcgym.py:300-316), as in
 // step_kernel<..., UNC>.
@@ -1729,6 +1145,7 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 }
 
 }  // namespace pcg
+#include "pcg_lean.hpp"
 #include "pcg_step_queue.hpp"
 #include "pcg_rollout_flat.hpp"
 #ifndef __HIPCC_RTC__  // (ahead-of-time kernels only: a run-time compiled plan has no closed-loop rollout)

@@ -91,31 +91,6 @@ PCG_DEV void constraint_rows_w(CDevConst& c, const Pack<W> (&x)[M::NX], const do
   }
 }
 
-// initial state of one env (pcgym.py:284-288, apply_uncertainties :255-261) and its observation rows: the draws of
-// reset_env / reset_lean, kept in registers so that the caller can merge them into a vector store
-template <class M>
-PCG_DEV void reset_vals(const StepArgs& A, CDevConst& c, uint64_t env_id, uint64_t seed, double (&xv)[M::NX],
-                        double (&ov)[M::NX]) {
-#pragma unroll
-  for (int i = 0; i < M::NX; ++i) {
-    double v = c.x0[i];
-    if (c.has_x0_unc && c.x0_unc[i] != 0.0) {
-      const double pct = c.x0_unc[i];
-      if (c.flags & PCG_F_X0_NORMAL) {
-        double z0, z1;
-        rng_normal2(seed, env_id, 0u, RNG_RESET + (uint32_t)(i >> 1), z0, z1);
-        v = c.x0[i] + pct * c.x0[i] * ((i & 1) ? z1 : z0);
-      } else {
-        double u0, u1;
-        rng_uniform2(seed, env_id, 0u, RNG_RESET + (uint32_t)(i >> 1), u0, u1);
-        v = c.x0[i] * (1 + pct * (2.0 * ((i & 1) ? u1 : u0) - 1.0));
-      }
-    }
-    xv[i] = v;
-    ov[i] = (v - c.omap[i].lo) * c.omap[i].sc + c.omap[i].off;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // One env step for the W envs of a lane, features by compile-time mask.  The batch is lock-stepped: the step
 // counter, the schedule values, the SP / disturbance slots are wave-uniform scalars.
@@ -293,12 +268,7 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
     if (k < nd) out.od[k] = (dv[k] - c.omap[NX + nso + k].lo) * c.omap[NX + nso + k].sc + c.omap[NX + nso + k].off;
   // ---- per-env health (PCG_ST_*): fixed-step RK4 cannot fail in the integrator, only leave a non-finite state ----
 #pragma unroll
-  for (int j = 0; j < W; ++j) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) ok = ok && (__builtin_fabs(x[i].v[j]) < __builtin_inf());
-    out.status[j] = ok ? PCG_ST_OK : PCG_ST_NONFINITE;
-  }
+  for (int j = 0; j < W; ++j) out.status[j] = nonfinite<NX, W>(x, j) ? PCG_ST_NONFINITE : PCG_ST_OK;
   // ---- same-launch auto-reset (pcg_step_autoreset): reward / done / viol / status of the finished step stay,
   //      state, observation and a_delta accumulator become those of the new episode ----
   out.reset = false;
@@ -311,7 +281,7 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
 #pragma unroll
       for (int j = 0; j < W; ++j) {
         double xv[NX], ov[NX];
-        reset_vals<M>(A, c, (uint64_t)(A.env_offset + e0 + j), A.reset_seed, xv, ov);
+        reset_vals<M>(A, c, NX, (uint64_t)(A.env_offset + e0 + j), A.reset_seed, xv, ov);
         if (done[j]) {
 #pragma unroll
           for (int i = 0; i < NX; ++i) {
@@ -339,6 +309,8 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
   }
 }
 
+// (store_feat and the unpack loop of step_kernel_feat keep their own form: on the tile I/O helpers of pcg_lean.hpp the same
+// bits came out 0.7-2.8 % slower than the parent's spread allows -- profiles/r10/lean_io_refactor.txt)
 template <class M, int W, unsigned FT>
 PCG_DEV void store_feat(const StepArgs& A, CDevConst& c, int64_t e0, const Pack<W> (&x)[M::NX],
                         const FeatOut<M, W>& out, bool nt) {

@@ -204,6 +204,59 @@ def test_status_reports_failed_and_nonfinite_steps():
         env.close()
 
 
+def _plant_nonfinite(env, B):
+    """the plant of test_status_reports_failed_and_nonfinite_steps: a NaN in env 5, an Inf in the last env"""
+    env.reset()
+    env.x[1, 5] = float("nan")
+    env.x[0, B - 1] = float("inf")
+
+
+def _assert_two_flagged(env, B):
+    from pcgym_amd import _abi as abi
+
+    st = env.status.cpu().numpy()
+    assert st[5] == abi.PCG_ST_NONFINITE and st[B - 1] == abi.PCG_ST_NONFINITE and st.sum() == 2 * abi.PCG_ST_NONFINITE
+
+
+@pytest.mark.parametrize("B,route", [(1024, "lean2"), (1023, "lean1")])
+def test_status_reports_nonfinite_states_of_the_lean_fused_rollout(B, route):
+    """the same plant through rollout_kernel_lean (T = 3, two envs per lane and one): its single check after the last
+    step flags exactly the two planted envs"""
+    torch = _torch()
+    from pcgym_amd import VecEnv
+
+    p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
+    p.update(integrator="rk4")
+    env = VecEnv(p, n_envs=B, seed=1)
+    _plant_nonfinite(env, B)
+    env.rollout(torch.zeros((3, 1, B), dtype=torch.float64, device=env.device))
+    torch.cuda.synchronize()
+    routes = H._rollout_routes(H._launch_names(env._lib))
+    assert set(routes) == {route}, routes
+    _assert_two_flagged(env, B)
+    env.close()
+
+
+def test_status_reports_nonfinite_states_of_a_feature_masked_step():
+    """the same plant through step_kernel_feat (constraint rows, two envs per lane), which carries the status of every env
+    in its output and writes the failures only"""
+    torch = _torch()
+    from pcgym_amd import VecEnv
+
+    B = 1024
+    p, kw, viol = H.feat_params("cstr", "cons")
+    env = VecEnv(copy.deepcopy(p), n_envs=B, seed=1, **kw)
+    if viol:
+        env._buf.viol = env.viol.data_ptr()
+    _plant_nonfinite(env, B)
+    env.step(torch.zeros((1, B), dtype=torch.float64, device=env.device))
+    torch.cuda.synchronize()
+    names = H._launch_names(env._lib)
+    assert any("16step_kernel_featI" in n for n in names), f"step_kernel_feat was not launched: {names}"
+    _assert_two_flagged(env, B)
+    env.close()
+
+
 def test_default_cstr_integrator_survives_the_ignition_branch():
     """SURVEY.md section 8(d) config 2's own x0 box U(0.7,1.0) x U(310,350) K at B = 2^20 with the DEFAULT integrator
     (adaptive: config.py): a quarter of these envs ignite (T -> 440..480 K), where fixed-step RK4 returned finite garbage
