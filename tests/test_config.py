@@ -244,6 +244,33 @@ def test_integrator_selection():
     assert EnvSpec(p).to_cfg()[0].integrator_id == abi.PCG_INT_TSIT5
 
 
+def test_integrator_plan_is_a_function_of_plain_values():
+    """rows of test_integrator_selection through config.integrator_plan directly: no EnvSpec, the same plan"""
+    from pcgym_amd.config import integrator_plan
+
+    rows = [("cstr_canonical", {}, 0), ("cstr_canonical", {"integrator": "rk4g"}, 0), ("four_tank_canonical", {}, 0),
+            ("me_canonical", {}, 0), ("me_canonical", {"integrator": "rodas4"}, 0), ("me_canonical", {"integration_method": "jax"}, 0),
+            ("me_canonical", {"uncertainty_percentages": {"Kla": 0.1}, "uncertainty_bounds": {"low": [4.0], "high": [6.0]}}, 1),
+            ("me_canonical", {"integrator": "rodas3", "rtol": 1e-6, "atol": 1e-8}, 0)]
+    for name, keys, nunc in rows:
+        p = P(name)
+        p.update(keys)
+        s = EnvSpec(p)
+        mi = M.get_model(p["model"])
+        got = integrator_plan(mi.model_id, mi.param_vector(), float(p["tsim"]) / p["N"], nunc, p.get("integration_method", "hip"),
+                              None, False, keys)
+        assert got == (s.integrator, s.substeps, s.rtol, s.atol, s.max_steps, s.ep_frac, s.ep_kmax, s.coop_thr), (name, keys)
+    pv = M.get_model("multistage_extraction").param_vector()
+    assert integrator_plan(M.ME, pv, 1.0, 0, "hip", None, False, {"integrator": "rodas4"}) == \
+        ("rodas4", 128, 3e-8, 3e-8, 100000, 0.5, 10, 60.0)
+    assert integrator_plan(M.ME, pv, 1.0, 0, "hip", None, True, {"integrator": "rodas4"})[-1] == 0.0  # run-time compiled rhs
+    assert integrator_plan(M.AFFINE, [], 0.2, 0, "hip", np.array([[-2.0, 1.1], [0.0, -0.5]]), False, {})[:2] == ("rk4", 13)  # ceil(0.2 * 3.1 / 0.05)
+    with pytest.raises(ValueError, match="use 'rk4' or 'dopri5'"):
+        integrator_plan(M.CSTR, M.get_model("cstr").param_vector(), 26 / 60, 1, "hip", None, False, {"integrator": "cv8"})
+    with pytest.raises(ValueError, match="needs a model with a guard hook: cstr"):
+        integrator_plan(M.ME, pv, 1.0, 0, "hip", None, False, {"integrator": "tsit5g"})
+
+
 def test_shape_errors():
     p = P("cstr_canonical")
     p["x0"] = np.array([0.8, 330, 0.8, 1.0])
