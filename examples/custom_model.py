@@ -6,7 +6,10 @@ expressions and compiled into the step kernels when the env is created (hipRTC, 
   * 65,536 envs, proportional control of the biomass set-point through the dilution rate, a non-affine constraint
     (also an expression) recorded per step, the feed concentration as a scheduled disturbance;
   * the same plant made numerically stiff (fast dilution dynamics): the explicit pair against the L-stable
-    Rosenbrock integrator (`integrator: 'rodas3'`).
+    Rosenbrock integrator (`integrator: 'rodas3'`);
+  * the chemostat without its constraint in FUSED closed loop: an `MLPPolicy` (and a Gaussian actor-critic) evaluated inside
+    the rollout kernel, one launch per episode -- the closed-loop kernels of a user model are compiled at the first such call
+    (`VecEnv.prepare_closed_loop()` does it ahead of time, e.g. before capturing the call into a graph).
 
 Needs an MI355X (there is no CPU path):  python examples/custom_model.py
 """
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pcgym_amd import make_vec_env  # noqa: E402
+from pcgym_amd import GaussianActorCritic, MLPPolicy, collect_onpolicy, collect_rollouts, make_vec_env  # noqa: E402
 
 N = 60
 # The model can also be handed over as a plain Python object in the reference's protocol (__call__(x, u) + info()): its
@@ -58,6 +61,44 @@ def episode(env, kp=4.0):
     return ret, viol
 
 
+def fused_closed_loop(B):
+    """the same proportional law as an MLPPolicy (affine state feedback, clipped): the whole episode in one launch.  The fused
+    calls take RK4 / cv8 plans without constraint rows, so the constraint is dropped here (a plan with constraints steps)."""
+    p = {k: v for k, v in env_params.items() if k not in ("constraints", "r_penalty", "done_on_cons_vio")}
+    p.update(integrator="rk4", substeps=8)
+    env, env_s = make_vec_env(p, n_envs=B, seed=0), make_vec_env(p, n_envs=B, seed=0)   # (same seed: the same initial states)
+    t0 = time.perf_counter()
+    env.prepare_closed_loop()   # (optional: the first fused call would do it)
+    print("closed-loop kernels of the user model ready in %.2f s (hipRTC the first time, a disk-cache hit afterwards)"
+          % (time.perf_counter() - t0))
+    kp = 4.0
+    pol = MLPPolicy([np.array([[kp, 0.0, -kp, 0.0]])], [np.zeros(1)], out_map="clip", out_low=-1.0, out_high=1.0)  # obs = [X, S, SP, Sf]
+    routes = {"fused (one launch)": lambda: collect_rollouts(env, policy=pol),
+              "per step (torch callable)": lambda: collect_rollouts(env_s, policy=lambda o: pol(o))}
+    out = {}
+    for name, fn in routes.items():
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out[name] = fn()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print("closed loop, %-26s %7.1f ms per episode of %d envs (%.2e env-steps/s), return %.3f"
+              % (name + ":", dt * 1e3, B, B * (N - 1) / dt, out[name]["r"].sum(dim=1).mean()))
+    a, b = out.values()
+    # (both envs are in their second episode: same draws of the initial states; what remains is the rounding of the policy)
+    print("largest difference between the two routes: x %.1e, u %.1e" % ((a["x"] - b["x"]).abs().max(), (a["u"] - b["u"]).abs().max()))
+    # what an on-policy trainer collects: sampled actions, log-probabilities, values and advantages, again in one launch
+    rng = np.random.default_rng(0)
+    critic = MLPPolicy([rng.standard_normal((16, 4)) / 2, rng.standard_normal((1, 16)) / 4], [np.zeros(16), np.zeros(1)], out_map="none")
+    ac = GaussianActorCritic(pol, np.full(1, -1.5), critic)
+    d = collect_onpolicy(env, ac, fused=True)
+    torch.cuda.synchronize()
+    print("on-policy batch: act %s, mean log-probability %.3f, mean advantage %.3f"
+          % (tuple(d["act"].shape), d["logp"].mean(), d["adv"].mean()))
+    env.close(), env_s.close(), ac.close()
+
+
 def main():
     B = 65536
     t0 = time.perf_counter()
@@ -83,6 +124,7 @@ def main():
               % (integ, (time.perf_counter() - t0) * 1e3, e.nsteps.sum(dim=0).double().mean(), int((e.status != 0).sum())))
         e.close()
     del x_ref
+    fused_closed_loop(B)
 
 
 if __name__ == "__main__":

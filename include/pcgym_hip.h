@@ -526,14 +526,27 @@ PCG_API int pcg_policy_update(pcg_policy* policy, const pcg_policy_cfg* cfg);
  *   - a_seq_out, obs_seq, rew_seq may each be NULL; layout, strides and 16-byte rules as in pcg_rollout_strided;
  *     io->x / obs / rew / done receive the last step, as in pcg_rollout.  io->a is not read.
  * Lock-stepped plans only (io->t == NULL: PCG_E_UNSUPPORTED otherwise).  PCG_E_DIM when the policy's n_in / n_out are not
- * the plan's Nobs / na.  PCG_E_UNSUPPORTED, before anything is launched: plans with constraint rows, per-env parameters,
- * user expressions or PCG_MODEL_USER, any integrator other than PCG_INT_RK4 / PCG_INT_CV8.
- * The call reads the plan and the policy and writes neither: no lazy allocation, no memset -- safe under stream capture
- * and from several streams at once (on distinct buffers). */
+ * the plan's Nobs / na.  PCG_E_UNSUPPORTED, before anything is launched: plans with constraint rows (user_cons_src
+ * included), per-env parameters, any integrator other than PCG_INT_RK4 / PCG_INT_CV8.
+ * A built-in plan's call reads the plan and the policy and writes neither: no lazy allocation, no memset -- safe under
+ * stream capture and from several streams at once (on distinct buffers).
+ * Plans with run-time compiled code (PCG_MODEL_USER, user_reward_src) run the same kernels from a second run-time compiled
+ * module of their own, which pcg_plan_create() does NOT build: the first closed-loop call of the plan (either entry point,
+ * after every argument check) or pcg_plan_prepare_closed_loop() builds or loads it -- hipRTC the first time, the caches of
+ * the step module afterwards; PCG_E_JIT, with pcg_last_jit_log(), if it does not compile.  Loading a module is not a
+ * capturable operation: while `stream` is being captured and the module does not exist yet the call returns
+ * PCG_E_UNSUPPORTED and launches nothing -- call pcg_plan_prepare_closed_loop(), or make one eager call, before capturing.
+ * Once the module exists the call is as capture-safe as a built-in plan's. */
 PCG_API int pcg_rollout_policy(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* policy, int32_t t0, int32_t T,
                                double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
                                int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                                int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
+
+/* Builds or loads the closed-loop module of a plan with run-time compiled code (see pcg_rollout_policy), on the plan's
+ * device, synchronously; idempotent.  PCG_OK and nothing done for a built-in plan, whatever its configuration;
+ * PCG_E_UNSUPPORTED for a run-time compiled plan neither closed-loop entry point takes (constraint rows, an integrator
+ * other than PCG_INT_RK4 / PCG_INT_CV8); PCG_E_JIT as at pcg_plan_create().  Not inside a stream capture. */
+PCG_API int pcg_plan_prepare_closed_loop(pcg_plan* plan);
 
 /* Closed-loop fused rollout with a STOCHASTIC actor-critic (ABI 16): what an on-policy trainer (PPO) collects, in one
  * launch.  The form is stable-baselines3's MlpPolicy: a Gaussian actor with a state-independent standard deviation and a
@@ -559,7 +572,8 @@ PCG_API int pcg_rollout_policy(pcg_plan* plan, const pcg_buffers* io, const pcg_
  * (n_in != Nobs or n_out != 1), PCG_E_VALUE (an output map); PCG_E_UNSUPPORTED for an actor with PCG_POL_TANH (a squashed
  * Gaussian needs the map's Jacobian in logp); PCG_E_NULL sigma == NULL; PCG_E_VALUE a sigma that is not finite and
  * positive; then T / t0 / buffers / strides as in pcg_rollout_policy.
- * Reads the plan and the policies and writes neither: safe under stream capture. */
+ * Reads the plan and the policies and writes neither: safe under stream capture (a plan with run-time compiled code: once
+ * its closed-loop module exists, as for pcg_rollout_policy). */
 #define PCG_RNG_POLICY 0x400
 PCG_API int pcg_rollout_actor(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* actor, const pcg_policy* critic,
                               const double* sigma, int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride,

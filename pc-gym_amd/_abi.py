@@ -205,6 +205,7 @@ EXPORTS = [
     "pcg_policy_destroy",
     "pcg_policy_update",
     "pcg_rollout_policy",
+    "pcg_plan_prepare_closed_loop",
     "pcg_rollout_actor",
     "pcg_actor_logp_const",
     "pcg_policy_noise",
@@ -268,6 +269,8 @@ def declare(lib):
     lib.pcg_rollout_policy.restype = C.c_int
     lib.pcg_rollout_policy.argtypes = [vp, C.POINTER(pcg_buffers), vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int64,
                                        vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_uint64, vp]
+    lib.pcg_plan_prepare_closed_loop.restype = C.c_int
+    lib.pcg_plan_prepare_closed_loop.argtypes = [vp]
     lib.pcg_policy_update.restype = C.c_int
     lib.pcg_policy_update.argtypes = [vp, C.POINTER(pcg_policy_cfg)]
     lib.pcg_rollout_actor.restype = C.c_int

@@ -11,6 +11,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <cerrno>
 #include <cstdlib>
 
@@ -102,6 +103,8 @@ static const double* const DEFAULTS[] = {DEF_CSTR,        DEF_FOUR_TANK, DEF_ME,
 
 using namespace pcg;
 
+struct JitSource;  // (with the run-time compilation, below)
+
 struct pcg_plan {
   uint32_t magic;
   int device;
@@ -130,6 +133,10 @@ struct pcg_plan {
   hipFunction_t jit_fn[2];  // run-time compiled general step kernel with user expressions [per_env_t] (or null)
   hipFunction_t jit_integ, jit_rhs;  // PCG_MODEL_USER: the run-time compiled test hooks (pcg_integrate / pcg_rhs)
   hipFunction_t jit_roll;            // run-time compiled fused rollout of a plan with user expressions (or null)
+  // the plan's SECOND module, the two closed-loop kernels: null until the first closed-loop call or
+  // pcg_plan_prepare_closed_loop builds it from jit_src (written once, under g_jit_mu; read with acquire)
+  hipFunction_t jit_pol, jit_act;
+  JitSource* jit_src;                // a run-time compiled plan's preamble (null for a built-in plan)
   int nx;                   // states (the kernel table's for built-in models, the cfg's for PCG_MODEL_USER)
   // work space of the barrier-free rollout (pcg_rollout_flat.hpp): 4 counters + 2 x flat_cap indices, allocated at the first
   // rollout that takes that path (and again if a later batch is larger) -- the only plan state a launch still writes
@@ -583,8 +590,12 @@ struct JitModule {
   hipFunction_t integ, rhs; // PCG_MODEL_USER only
   hipFunction_t roll;       // fused rollout kernel (null for the Rosenbrock integrators: their matrices live in LDS)
 };
+// what a plan keeps of its configuration to build its closed-loop module later (jit_closed_loop)
+struct JitSource {
+  std::string preamble, include_dir;
+  int kid, integrator_id;
+};
 static std::mutex g_jit_mu;
-static std::map<uint64_t, JitModule> g_jit_cache;
 static std::string g_jit_log;
 
 static uint64_t fnv1a(const std::string& s) {
@@ -703,13 +714,11 @@ static void jit_cache_write(const std::string& path, int nfn, const std::string&
   if (!ok || std::rename(tmp.c_str(), path.c_str()) != 0) ::unlink(tmp.c_str());
 }
 
-static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* out) {
-  if (!cfg->jit_include_dir) return PCG_E_NULL;
+// What every translation unit of a plan opens with: the user's macros, the kernel headers, the check that they are the ones
+// this library was built from, and the user's source as pcg_user_rhs / pcg_user_constraints / pcg_user_reward.  The step
+// module (jit_kernels) and the closed-loop module (jit_closed_loop) differ only in what follows it.
+static std::string jit_preamble(const pcg_env_cfg* cfg) {
   const bool user = cfg->model_id == PCG_MODEL_USER;
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  std::string arch = prop.gcnArchName;
-  arch = arch.substr(0, arch.find(':'));
   std::ostringstream src;
   if (user)
     src << "#define PCG_USER_NX " << cfg->nx << "\n#define PCG_USER_NA " << cfg->na << "\n#define PCG_USER_NDM " << cfg->ndm
@@ -730,43 +739,31 @@ static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* o
     src << "__device__ double pcg_user_reward(const double* o, const double* x, const double* u, const double* sp, "
            "int violated, int t, int N) {\n  return (double)(" << cfg->user_reward_src << ");\n}\n";
   src << "}\n";
-  const bool roll = cfg->integrator_id != PCG_INT_RODAS3 && !is_ros_pair(cfg->integrator_id);
-  const int iroll = user ? 4 : 2;
-  const int nfn = iroll + (roll ? 1 : 0);
-  std::string names[5];
-  for (int pe = 0; pe < 2; ++pe) {
-    std::ostringstream nm;
-    nm << "pcg::step_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", " << (pe ? "true" : "false")
-       << ", false, true, false>";
-    names[pe] = nm.str();
-    src << "template __global__ void " << names[pe] << "(const pcg::StepArgs);\n";
-  }
-  if (user) {
-    std::ostringstream ni, nr;
-    ni << "pcg::integrate_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", false>";
-    nr << "pcg::rhs_kernel<pcg::Model<" << kid << "> >";
-    names[2] = ni.str();
-    names[3] = nr.str();
-    src << "template __global__ void " << names[2] << "(pcg::CDevConst*, int64_t, int, double*, const double*, int32_t*);\n";
-    src << "template __global__ void " << names[3] << "(pcg::CDevConst*, int64_t, int, const double*, const double*, double*);\n";
-  }
-  if (roll) {  // pcg_rollout for plans with user expressions: T steps with the state in registers
-    std::ostringstream nm;
-    nm << "pcg::rollout_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", false>";
-    names[iroll] = nm.str();
-    src << "template __global__ void " << names[iroll] << "(const pcg::StepArgs);\n";
-  }
-  const std::string text = src.str();
+  return src.str();
+}
+
+constexpr int JIT_MAX_FN = 5;  // kernels of one run-time compiled module
+using JitFns = std::array<hipFunction_t, JIT_MAX_FN>;
+static std::map<uint64_t, JitFns> g_jit_cache;
+
+// One translation unit -> one module: fns[q] = the kernel names[q] (a name expression of `text`), q < nfn.  Looked up in the
+// process (by text, architecture, ABI, header digest, build id and device), then on disk, then compiled with hipRTC.
+// The caller holds g_jit_mu.
+static int jit_module(const std::string& text, const std::string* names, int nfn, const std::string& inc_dir, int device,
+                      JitFns* fns) {
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  std::string arch = prop.gcnArchName;
+  arch = arch.substr(0, arch.find(':'));
   // The translation unit only says `#include "pcg_kernels.hpp"`: the CONTENT of the kernel headers it will be compiled
   // against has to be part of the key too (a changed integrator or model with unchanged struct sizes must not find an
   // old code object) -- hash of every header in the include directory + the ABI header + the library's own build id.
-  const std::string hdr = jit_header_digest(cfg->jit_include_dir);
+  const std::string hdr = jit_header_digest(inc_dir.c_str());
   const std::string ident = text + "|" + arch + "|" + std::to_string(PCG_ABI_VERSION) + "|" + hdr + "|" PCG_SRC_HASH;
   const uint64_t key = fnv1a(ident + "|" + std::to_string(device));
-  std::lock_guard<std::mutex> lk(g_jit_mu);
   auto hit = g_jit_cache.find(key);
   if (hit != g_jit_cache.end()) {
-    *out = hit->second;
+    *fns = hit->second;
     return PCG_OK;
   }
   // disk cache: one file per source = lowered kernel names + code object, with a digest of both
@@ -774,14 +771,14 @@ static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* o
   char hex[40];
   std::snprintf(hex, sizeof(hex), "%016llx%016llx", (unsigned long long)fnv1a(ident), (unsigned long long)fnv1a_seed(ident, 0x9E3779B97F4A7C15ull));
   const std::string path = dir.empty() ? std::string() : dir + "/" + hex + ".pco";
-  std::string code, low[5];
+  std::string code, low[JIT_MAX_FN];
   bool from_disk = !path.empty() && jit_cache_read(path, nfn, &code, low);
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (code.empty()) {
       hiprtcProgram prog;
       if (hiprtcCreateProgram(&prog, text.c_str(), "pcg_user_step.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return PCG_E_JIT;
       for (int q = 0; q < nfn; ++q) hiprtcAddNameExpression(prog, names[q].c_str());
-      const std::string oarch = "--offload-arch=" + arch, oinc = std::string("-I") + cfg->jit_include_dir;
+      const std::string oarch = "--offload-arch=" + arch, oinc = "-I" + inc_dir;
       const char* opts[] = {oarch.c_str(), "-O3", "-std=c++17", oinc.c_str()};
       const hiprtcResult cr = hiprtcCompileProgram(prog, 4, opts);
       size_t ls = 0;
@@ -819,19 +816,80 @@ static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* o
       }
       return (int)le;
     }
-    JitModule jm;
-    jm.integ = jm.rhs = jm.roll = nullptr;
-    if (roll) HIP_TRY(hipModuleGetFunction(&jm.roll, mod, low[iroll].c_str()));
-    for (int pe = 0; pe < 2; ++pe) HIP_TRY(hipModuleGetFunction(&jm.fn[pe], mod, low[pe].c_str()));
-    if (user) {
-      HIP_TRY(hipModuleGetFunction(&jm.integ, mod, low[2].c_str()));
-      HIP_TRY(hipModuleGetFunction(&jm.rhs, mod, low[3].c_str()));
-    }
-    g_jit_cache[key] = jm;
-    *out = jm;
+    JitFns got{};
+    for (int q = 0; q < nfn; ++q) HIP_TRY(hipModuleGetFunction(&got[q], mod, low[q].c_str()));
+    g_jit_cache[key] = got;
+    *fns = got;
     return PCG_OK;
   }
   return PCG_E_JIT;
+}
+
+static int jit_kernels(const pcg_env_cfg* cfg, int kid, int device, JitModule* out) {
+  if (!cfg->jit_include_dir) return PCG_E_NULL;
+  const bool user = cfg->model_id == PCG_MODEL_USER;
+  std::ostringstream src;
+  src << jit_preamble(cfg);
+  const bool roll = cfg->integrator_id != PCG_INT_RODAS3 && !is_ros_pair(cfg->integrator_id);
+  const int iroll = user ? 4 : 2;
+  const int nfn = iroll + (roll ? 1 : 0);
+  std::string names[JIT_MAX_FN];
+  for (int pe = 0; pe < 2; ++pe) {
+    std::ostringstream nm;
+    nm << "pcg::step_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", " << (pe ? "true" : "false")
+       << ", false, true, false>";
+    names[pe] = nm.str();
+    src << "template __global__ void " << names[pe] << "(const pcg::StepArgs);\n";
+  }
+  if (user) {
+    std::ostringstream ni, nr;
+    ni << "pcg::integrate_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", false>";
+    nr << "pcg::rhs_kernel<pcg::Model<" << kid << "> >";
+    names[2] = ni.str();
+    names[3] = nr.str();
+    src << "template __global__ void " << names[2] << "(pcg::CDevConst*, int64_t, int, double*, const double*, int32_t*);\n";
+    src << "template __global__ void " << names[3] << "(pcg::CDevConst*, int64_t, int, const double*, const double*, double*);\n";
+  }
+  if (roll) {  // pcg_rollout for plans with user expressions: T steps with the state in registers
+    std::ostringstream nm;
+    nm << "pcg::rollout_kernel<pcg::Model<" << kid << ">, " << cfg->integrator_id << ", false>";
+    names[iroll] = nm.str();
+    src << "template __global__ void " << names[iroll] << "(const pcg::StepArgs);\n";
+  }
+  JitFns fns;
+  std::lock_guard<std::mutex> lk(g_jit_mu);
+  PCG_TRY(jit_module(src.str(), names, nfn, cfg->jit_include_dir, device, &fns));
+  out->fn[0] = fns[0];
+  out->fn[1] = fns[1];
+  out->integ = user ? fns[2] : nullptr;
+  out->rhs = user ? fns[3] : nullptr;
+  out->roll = roll ? fns[iroll] : nullptr;
+  return PCG_OK;
+}
+
+// The closed-loop module of a run-time compiled plan: rollout_policy_kernel and rollout_actor_kernel of the plan's model and
+// integrator behind the plan's own preamble (JitSource, kept from pcg_plan_create).  Built at the plan's first closed-loop
+// call or by pcg_plan_prepare_closed_loop, never at creation: a plan that only steps pays nothing for it.  Same caches, same
+// lock and same statuses as the step module.
+static int jit_closed_loop(const JitSource& js, int device, hipFunction_t* pol, hipFunction_t* act) {
+  std::ostringstream src;
+  src << js.preamble << "static_assert(sizeof(pcg::PolicyArgs) == " << sizeof(PolicyArgs) << " && sizeof(pcg::ActorArgs) == "
+      << sizeof(ActorArgs) << " && sizeof(pcg::PolicyDev) == " << sizeof(PolicyDev)
+      << ", \"closed-loop kernel headers differ from the ones libpcgym_hip.so was built from\");\n";
+  std::string names[JIT_MAX_FN];
+  const char* kern[2] = {"rollout_policy_kernel", "rollout_actor_kernel"};
+  const char* args[2] = {"PolicyArgs", "ActorArgs"};
+  for (int q = 0; q < 2; ++q) {
+    std::ostringstream nm;
+    nm << "pcg::" << kern[q] << "<pcg::Model<" << js.kid << ">, " << js.integrator_id << ">";
+    names[q] = nm.str();
+    src << "template __global__ void " << names[q] << "(const pcg::StepArgs, const pcg::" << args[q] << ");\n";
+  }
+  JitFns fns;
+  PCG_TRY(jit_module(src.str(), names, 2, js.include_dir, device, &fns));
+  *pol = fns[0];
+  *act = fns[1];
+  return PCG_OK;
 }
 
 // ---- launch geometry ------------------------------------------------------------------------------------------
@@ -1014,6 +1072,11 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
     p->jit_integ = jm.integ;
     p->jit_rhs = jm.rhs;
     p->jit_roll = jm.roll;
+    p->jit_src = new (std::nothrow) JitSource{jit_preamble(cfg), cfg->jit_include_dir, p->kid, cfg->integrator_id};
+    if (!p->jit_src) {
+      (void)pcg_plan_destroy(p);
+      return (int)hipErrorOutOfMemory;
+    }
     // Rosenbrock pairs keep nx^2 doubles per lane in LDS: past 48 KB per workgroup (nx >= 10) a kernel has to be told.
     // Decided HERE, so that a plan that cannot run says so at creation and not at its first step.
     const int jnx = cfg->model_id == PCG_MODEL_USER ? cfg->nx : kernels(p->kid).nx;
@@ -1051,6 +1114,7 @@ int pcg_plan_destroy(pcg_plan* p) {
   p->magic = 0;
   hipError_t e1 = hipFree(p->dC), e2 = hipFree(p->dsched);
   if (p->flat_ws) (void)hipFree(p->flat_ws);
+  delete p->jit_src;
   delete p;
   if (e1 != hipSuccess) return (int)e1;
   if (e2 != hipSuccess) return (int)e2;
@@ -1694,6 +1758,34 @@ struct SeqRec {  // a sequence the head records, with its component stride; null
   int64_t comp_stride;
 };
 
+// whether a closed-loop kernel exists for this run-time compiled plan: the plans the built-in path takes
+static bool jit_closed_loop_ok(const pcg_plan* p) {
+  return p->hc.ncon <= 0 && p->hc.nunc <= 0 && lean_scheme(p->integrator_id) >= 0;
+}
+
+// Builds or loads the closed-loop module of a run-time compiled plan; a second call finds it there.
+static int jit_prepare_closed_loop(pcg_plan* p) {
+  if (__atomic_load_n(&p->jit_pol, __ATOMIC_ACQUIRE)) return PCG_OK;
+  std::lock_guard<std::mutex> lk(g_jit_mu);
+  if (p->jit_pol) return PCG_OK;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device) HIP_TRY(hipSetDevice(p->device));  // (the module is loaded on the plan's device, as at creation)
+  hipFunction_t pol = nullptr, act = nullptr;
+  int rc = jit_closed_loop(*p->jit_src, p->device, &pol, &act);
+  if (dev != p->device) {
+    const hipError_t e = hipSetDevice(dev);
+    if (rc == PCG_OK) rc = (int)e;
+  }
+  PCG_TRY(rc);
+  p->jit_act = act;
+  __atomic_store_n(&p->jit_pol, pol, __ATOMIC_RELEASE);
+  return PCG_OK;
+}
+
+static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return p->jit_pol; }
+static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
+
 template <class Fn>
 static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2], StepArgs* a,
                             Fn* fn) {
@@ -1701,12 +1793,13 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   if (!q) return PCG_E_NULL;
   if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
   const DevConst& c = p->hc;
-  // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, run-time compiled
-  // models / expressions, and every integrator but the two fixed-step schemes
+  // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, and every integrator
+  // but the two fixed-step schemes
   const int ls = lean_scheme(p->integrator_id);
-  if (io->t || c.ncon > 0 || c.nunc > 0 || p->model_id == PCG_MODEL_USER || p->jit_fn[0] || ls < 0) return PCG_E_UNSUPPORTED;
-  *fn = (kernels(p->kid).*table)[ls];
-  if (!*fn) return PCG_E_UNSUPPORTED;
+  if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
+  // (a run-time compiled plan has no ahead-of-time kernel: closed_loop_launch takes its own module's)
+  *fn = p->jit_fn[0] ? nullptr : (kernels(p->kid).*table)[ls];
+  if (!*fn && !p->jit_fn[0]) return PCG_E_UNSUPPORTED;
   if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
   return PCG_OK;
 }
@@ -1727,6 +1820,21 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
   a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
   a.obs_seq = r.obs_seq; a.rew_seq = r.rew_seq;
   a.o_ss = r.obs_ss; a.o_cs = r.obs_cs; a.r_ss = r.rew_ss;
+  if (p->jit_fn[0]) {  // the plan's closed-loop module, built at its first use -- which must not be inside a stream capture
+    if (!__atomic_load_n(&p->jit_pol, __ATOMIC_ACQUIRE)) {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return PCG_E_UNSUPPORTED;
+      }
+      if (cap != hipStreamCaptureStatusNone) return PCG_E_UNSUPPORTED;  // (loading a module is not a capturable operation)
+      PCG_TRY(jit_prepare_closed_loop(p));
+    }
+    HeadArgs h = head;
+    void* argv[2] = {&a, &h};
+    return (int)hipModuleLaunchKernel(cov_jit(jit_head_fn(p, head)), grid_for(io->B), 1, 1, BLOCK, 1, 1, 0, (hipStream_t)stream,
+                                      argv, nullptr);
+  }
   hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head);
   return (int)hipGetLastError();
 }
@@ -1745,6 +1853,13 @@ int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, 
   pa.record_next = record_next_action ? 1 : 0;
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, stream);
+}
+
+int pcg_plan_prepare_closed_loop(pcg_plan* p) {
+  if (!plan_ok(p)) return PCG_E_PLAN;
+  if (!p->jit_fn[0]) return PCG_OK;  // a built-in plan's closed-loop kernels are in the library
+  if (!jit_closed_loop_ok(p)) return PCG_E_UNSUPPORTED;
+  return jit_prepare_closed_loop(p);
 }
 
 // ---- ... with a Gaussian actor and an optional critic (pcg_rollout_actor.hpp) -------------------------------------------

@@ -1148,13 +1148,14 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_lean.hpp"
 #include "pcg_step_queue.hpp"
 #include "pcg_rollout_flat.hpp"
-#ifndef __HIPCC_RTC__  // (ahead-of-time kernels only: a run-time compiled plan has no closed-loop rollout)
+// (also under hipRTC: a plan's second run-time compiled module instantiates the two closed-loop kernels, pcg_abi.hip jit_closed_loop)
 #include "pcg_rollout_policy.hpp"
 #include "pcg_rollout_actor.hpp"
-#endif
 namespace pcg {
 
 using StepFn = void (*)(const StepArgs);
+using PolFn = void (*)(const StepArgs, const PolicyArgs);
+using ActFn = void (*)(const StepArgs, const ActorArgs);
 
 #ifndef __HIPCC_RTC__
 // ---------------------------------------------------------------------------
@@ -1162,8 +1163,6 @@ using StepFn = void (*)(const StepArgs);
 // ---------------------------------------------------------------------------
 using RhsKFn = void (*)(CDevConst*, int64_t, int, const double*, const double*, double*);
 using IntKFn = void (*)(CDevConst*, int64_t, int, double*, const double*, int32_t*);
-using PolFn = void (*)(const StepArgs, const PolicyArgs);
-using ActFn = void (*)(const StepArgs, const ActorArgs);
 
 // one instantiation of the feature-masked small-model kernel (pcg_step_feat.hpp): serves every launch whose
 // needs are a subset of `mask`

@@ -314,6 +314,16 @@ class VecEnv:
         return [torch.empty(shape, dtype=torch.float64, device=self.device) if wanted else None
                 for shape, wanted in shape_wanted]
 
+    def prepare_closed_loop(self):
+        """Build or load the closed-loop kernels of a plan with run-time compiled code (a user model, a reward expression)
+        now instead of at the first ``rollout_policy`` / ``rollout_actor`` / fused ``collect_*`` call: a caller who records
+        those calls into a graph (``torch.cuda.graph``) has to, since a module cannot be loaded while a stream is being
+        captured.  Does nothing on a built-in plan; a second call does nothing; a run-time compiled plan the closed-loop
+        kernels do not take (constraints, integrators other than rk4 / cv8) raises PcgError."""
+        with _torch().cuda.device(self.device):
+            _lib.check(self._lib.pcg_plan_prepare_closed_loop(self._plan), "pcg_plan_prepare_closed_loop")
+        return self
+
     def rollout_policy(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
                        record_next_action=False):
         """Fused CLOSED-loop rollout: T steps in one launch, ``policy`` (an :class:`~pcgym_amd.policy.MLPPolicy`)
@@ -321,7 +331,8 @@ class VecEnv:
         Returns (a_seq (T [+1], na, B) | None, obs_seq (T, Nobs, B) | None, rew_seq (T, B) | None): the policy outputs
         as the caller would have passed them to step(); with ``record_next_action`` row T is the policy's proposal for
         the observation after the last step, not applied.  Plans the kernel does not take (constraints, per-env
-        parameters, user models, integrators other than rk4 / cv8) raise PcgError: loop over step() for those."""
+        parameters, integrators other than rk4 / cv8) raise PcgError: loop over step() for those.  A user model or a
+        plan with a reward expression compiles its closed-loop kernels at the first such call (``prepare_closed_loop``)."""
         if self.per_env_t:
             raise ValueError("rollout_policy() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)

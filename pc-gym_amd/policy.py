@@ -193,10 +193,10 @@ class MLPPolicy:
 
 
 def fused_policy_ok(spec, policy):
-    """the plans pcg_rollout_policy takes (include/pcgym_hip.h): fixed-step RK4 / CV8, no constraint rows, no per-env
-    parameters, nothing run-time compiled -- and a policy of the plan's sizes that the device form can hold"""
+    """the plans pcg_rollout_policy takes (include/pcgym_hip.h): fixed-step RK4 / CV8, no constraint rows (a constraint
+    expression is ``ncon`` rows too), no per-env parameters -- user models and reward expressions included, which run the
+    kernel from their plan's own run-time compiled module -- and a policy of the plan's sizes that the device form can hold"""
     return (isinstance(policy, MLPPolicy) and spec.integrator in ("rk4", "cv8") and not spec.ncon and not spec.nunc
-            and spec.user_rhs_src is None and not spec.user_reward_src and not spec.user_cons_src
             and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
 
 

@@ -75,7 +75,7 @@ def collect_rollouts(env, policy=None, actions=None):
 
     policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop); an ``MLPPolicy`` is evaluated inside
               the fused rollout kernel when the plan qualifies (``fused_policy_ok``: RK4 / CV8, no constraint rows, no
-              per-env parameters, no user model) and like any other callable otherwise, or
+              per-env parameters; user models and reward expressions included) and like any other callable otherwise, or
     actions : (N, na, B) tensor of policy outputs (open loop; row N-1 is only recorded in ``u``).
 
     Recording is zero-copy: each step's kernel writes its observation / reward rows straight into the trajectory
@@ -197,7 +197,7 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
         adv, ret (N-1, B)  from :func:`gae`
 
     Route: ONE launch (``pcg_rollout_actor``) when the plan and the networks qualify (``fused_actor_ok``: RK4 / CV8, no
-    constraint rows, no per-env parameters, no user model, no tanh map); otherwise -- or with ``fused=False`` -- one
+    constraint rows, no per-env parameters, no tanh map; user models and reward expressions included); otherwise -- or with ``fused=False`` -- one
     ``env.step`` per step with the sample formed in torch from ``env.policy_noise``, i.e. from the same random bits."""
     torch = _torch()
     s = env.spec
