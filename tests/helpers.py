@@ -371,11 +371,13 @@ def _make(p, B, **kw):
     return VecEnv(copy.deepcopy(p), n_envs=B, **kw)
 
 
-def make_policy(spec, obs0, hidden, seed):
+def make_policy(spec, obs0, hidden, seed, activation="tanh", out_map="clip", out_low=None, out_high=None):
     """Fixed-seed weights, scaled by the plan's own boxes so that the units are not saturated and a fair share of the outputs
     lies strictly inside the clip box: the first layer divides each input by the size of its observation box (1 when the plan
     normalises) and is centred on the mean reset observation, the output layer spans about the action box's half width around
-    its middle."""
+    its middle.  `activation` and `out_map` are MLPPolicy's; the clip box is the whole action box unless `out_low` / `out_high`
+    say otherwise.  Under out_map "tanh" the output layer spans [-1, 1] whatever the action box (the map's own range).  The
+    random draws do not depend on these four arguments."""
     from pcgym_amd import MLPPolicy
 
     rng = np.random.default_rng(seed)
@@ -385,7 +387,7 @@ def make_policy(spec, obs0, hidden, seed):
     else:
         s_in = np.maximum(np.maximum(np.abs(spec.o_low), np.abs(spec.o_high)), 1e-3)
     centre = np.mean(obs0, axis=1)
-    if spec.normalise_a:
+    if spec.normalise_a or out_map == "tanh":
         lo, hi = -np.ones(n_out), np.ones(n_out)
     else:
         lo, hi = np.asarray(spec.a_low, dtype=float), np.asarray(spec.a_high, dtype=float)
@@ -401,7 +403,8 @@ def make_policy(spec, obs0, hidden, seed):
             W = W / s_in[None, :]
             b = b - W @ centre
         Ws.append(W), bs.append(b)
-    return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=float(lo.min()), out_high=float(hi.max()))
+    return MLPPolicy(Ws, bs, activation=activation, out_map=out_map, out_low=float(lo.min()) if out_low is None else float(out_low),
+                     out_high=float(hi.max()) if out_high is None else float(out_high))
 
 
 def gamma(n):
