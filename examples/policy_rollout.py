@@ -16,6 +16,7 @@ shows the refresh a training loop does after an optimiser step (GaussianActorCri
 
 Needs an MI355X (there is no CPU path):  python examples/policy_rollout.py
 """
+import copy
 import os
 import sys
 import time
@@ -60,7 +61,25 @@ def main():
     diff = max(float((out["fused"][k] - out["per step"][k]).abs().max()) for k in ("x", "u", "r"))
     print(f"largest difference between the two routes over x, u, r: {diff:.2e} (two fp64 summation orders through a closed loop)")
     policy.close()
+    float32_leg(net, B)
     actor_critic(net, B)
+
+
+def float32_leg(net, B):
+    """the network as stable-baselines3 holds it -- a float32 module -- evaluated in float32 inside the kernel: its parameters
+    are kept bit for bit, every recorded action is a float32 value, the env arithmetic stays fp64"""
+    net32 = copy.deepcopy(net).float()  # (the caller's module stays as it is)
+    policy32 = MLPPolicy.from_torch(net32, out_map="clip", out_low=-1.0, out_high=1.0, dtype="float32")
+    env = make_vec_env(env_params, n_envs=B, seed=0)
+    collect_rollouts(env, policy=policy32)  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d = collect_rollouts(env, policy=policy32)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"fused, float32 policy: {dt * 1e3:7.2f} ms per episode of {B} envs ({B * (N - 1) / dt:.2e} env-steps/s)  "
+          f"mean return {d['r'].sum(dim=1).mean().item():.3f}")
+    env.close(), policy32.close()
 
 
 def actor_critic(actor_net, B):

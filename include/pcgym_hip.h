@@ -515,6 +515,25 @@ PCG_API int pcg_policy_destroy(pcg_policy* policy);
  * the policy is unchanged. */
 PCG_API int pcg_policy_update(pcg_policy* policy, const pcg_policy_cfg* cfg);
 
+/* The same policy evaluated in FLOAT32 inside the kernel (additive under ABI 16): stable-baselines3's MlpPolicy is a float32
+ * module, and policy.predict(obs) in the reference is a float32 forward pass.  Takes pcg_policy_create()'s cfg; weights,
+ * biases, out_low and out_high are rounded to the nearest float32 on upload.  The statuses of pcg_policy_validate(), plus
+ * PCG_E_VALUE for a value that is not finite after rounding.  pcg_policy_update() keeps a policy's dtype (and rounds alike).
+ * The arithmetic (csrc/pcg_rollout_policy_f32.hpp): in32[i] = (float)obs[i]; per unit one IEEE float32 FMA per input,
+ * ascending, from the bias; tanhf / ReLU; the last layer's output widened to double exactly.  pcg_rollout_policy:
+ * PCG_POL_NONE / PCG_POL_CLIP act on the widened value with the rounded box, PCG_POL_TANH is tanhf before the widening --
+ * every recorded output is a float32 value.  pcg_rollout_actor: mu and value are the widened outputs; u, a, logp are formed
+ * in fp64 exactly as for a float64 policy.  The env arithmetic is fp64 whatever the policy's dtype.
+ * Both entry points keep their signatures and dispatch on the policy's dtype.  What a float32 policy adds to their
+ * statuses, after every other check and with nothing compiled or launched: PCG_E_UNSUPPORTED on a plan with run-time
+ * compiled code (PCG_MODEL_USER, user_reward_src: the plan's closed-loop module carries the float64 kernels only -- step
+ * such a plan instead), and PCG_E_UNSUPPORTED for an actor and a critic of different dtypes. */
+#define PCG_POL_F64 0
+#define PCG_POL_F32 1
+PCG_API int pcg_policy_create_f32(pcg_policy** out, const pcg_policy_cfg* cfg);
+/* PCG_POL_F64 | PCG_POL_F32; PCG_E_NULL / PCG_E_PLAN for what is not a policy. */
+PCG_API int pcg_policy_dtype(const pcg_policy* policy);
+
 /* T env steps in ONE launch with the state in registers and the policy evaluated in the kernel between two steps:
  *   - the action of step s is policy(observation the env emitted before step s); for s = 0 that is io->obs as
  *     pcg_reset or the previous call left it.  The observation is exactly what pcg_step would have written (normalised

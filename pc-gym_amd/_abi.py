@@ -72,6 +72,8 @@ PCG_POL_NONE = 0
 PCG_POL_CLIP = 1
 PCG_POL_TANH = 2
 PCG_POL_MAX_WIDTH = 64
+PCG_POL_F64 = 0
+PCG_POL_F32 = 1
 PCG_RNG_POLICY = 0x400
 
 _pd = C.POINTER(C.c_double)
@@ -204,6 +206,8 @@ EXPORTS = [
     "pcg_policy_create",
     "pcg_policy_destroy",
     "pcg_policy_update",
+    "pcg_policy_create_f32",
+    "pcg_policy_dtype",
     "pcg_rollout_policy",
     "pcg_plan_prepare_closed_loop",
     "pcg_rollout_actor",
@@ -264,6 +268,10 @@ def declare(lib):
     lib.pcg_policy_validate.argtypes = [C.POINTER(pcg_policy_cfg)]
     lib.pcg_policy_create.restype = C.c_int
     lib.pcg_policy_create.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg)]
+    lib.pcg_policy_create_f32.restype = C.c_int
+    lib.pcg_policy_create_f32.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg)]
+    lib.pcg_policy_dtype.restype = C.c_int
+    lib.pcg_policy_dtype.argtypes = [vp]
     lib.pcg_policy_destroy.restype = C.c_int
     lib.pcg_policy_destroy.argtypes = [vp]
     lib.pcg_rollout_policy.restype = C.c_int

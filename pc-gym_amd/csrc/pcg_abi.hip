@@ -1622,6 +1622,7 @@ struct pcg_policy {
   int n_hidden, width[2], out_map;  // the shape pcg_policy_update holds a new cfg against; the map pcg_rollout_actor asks for
   size_t blob_doubles;              // size of the device block
   PolicyDev* dP;  // header + packed weights; rewritten only by pcg_policy_update (same shape, same block)
+  int dtype;      // PCG_POL_F64 | PCG_POL_F32: which packing the block holds, hence which kernel family reads it
 };
 static constexpr uint32_t POLICY_MAGIC = 0x50434750u;  // 'PCGP'
 
@@ -1687,16 +1688,63 @@ static std::vector<double> pack_policy(const pcg_policy_cfg* c) {
   return blob;
 }
 
-int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) {
+// The float32 form of the device block (pcg_rollout_policy_f32.hpp): the same header, then floats -- every value rounded to
+// nearest, the rows of two consecutive units interleaved (element (r, k) at offW + ((r / 2) ld + k) 2 + (r & 1)), rows padded
+// to an even count (POL_HB / POL_SB / POL32_OR), columns as in the fp64 form.  The header's clip box holds the rounded
+// bounds.  Returned in doubles' worth of storage, so that create / update treat both forms alike.
+// PCG_E_VALUE through *rc for a value that is not finite after rounding.
+static std::vector<double> pack_policy_f32(const pcg_policy_cfg* c, int* rc) {
+  auto up = [](int n, int m) { return (n + m - 1) / m * m; };
+  *rc = PCG_OK;
+  auto r32 = [&](double v) {
+    const float f = (float)v;
+    if (!std::isfinite(f)) *rc = PCG_E_VALUE;
+    return f;
+  };
+  PolicyDev h;
+  std::memset(&h, 0, sizeof(h));
+  h.n_in = c->n_in; h.n_out = c->n_out; h.n_hidden = c->n_hidden; h.act = c->activation; h.out_map = c->out_map;
+  h.out_lo = (double)(float)c->out_low; h.out_hi = (double)(float)c->out_high;
+  if (c->out_map == PCG_POL_CLIP && !(std::isfinite(h.out_lo) && std::isfinite(h.out_hi))) *rc = PCG_E_VALUE;
+  for (int l = 0; l < c->n_hidden; ++l) h.w[l] = c->width[l];
+  std::vector<float> data;
+  for (int l = 0; l <= c->n_hidden; ++l) {
+    int rows, cols;
+    policy_layer_dims(c, l, &rows, &cols);
+    const bool outl = l == c->n_hidden;
+    const int prow = outl ? POL32_OR : up(rows, l == 0 ? POL_HB : POL_SB);
+    const int pcol = l == 0 ? up(cols, POL_IB) : up(cols, l == 1 ? POL_HB : POL_SB);
+    h.ld[l] = pcol;
+    h.offW[l] = (int32_t)data.size();
+    data.resize(data.size() + (size_t)prow * pcol, 0.0f);
+    for (int r = 0; r < rows; ++r)
+      for (int k = 0; k < cols; ++k)
+        data[(size_t)h.offW[l] + ((size_t)(r / 2) * pcol + k) * 2 + (r & 1)] = r32(c->W[l][(size_t)r * cols + k]);
+    h.offb[l] = (int32_t)data.size();
+    data.resize(data.size() + (size_t)prow, 0.0f);
+    for (int r = 0; r < rows; ++r) data[(size_t)h.offb[l] + r] = r32(c->b[l][r]);
+  }
+  // (slack as in the fp64 form: no scalar fetch ends outside the block)
+  const size_t words = (data.size() + 32 + 1) / 2;
+  std::vector<double> blob(sizeof(PolicyDev) / sizeof(double) + words, 0.0);
+  std::memcpy(blob.data(), &h, sizeof(h));
+  std::memcpy(blob.data() + sizeof(PolicyDev) / sizeof(double), data.data(), sizeof(float) * data.size());
+  return blob;
+}
+
+static int policy_create(pcg_policy** out, const pcg_policy_cfg* cfg, int dtype) {
   if (!out) return PCG_E_NULL;
   *out = nullptr;
   PCG_TRY(pcg_policy_validate(cfg));
+  int prc = PCG_OK;
+  const std::vector<double> blob = dtype == PCG_POL_F32 ? pack_policy_f32(cfg, &prc) : pack_policy(cfg);
+  PCG_TRY(prc);
   pcg_policy* q = new (std::nothrow) pcg_policy();
   if (!q) return (int)hipErrorOutOfMemory;
+  q->dtype = dtype;
   q->n_in = cfg->n_in; q->n_out = cfg->n_out;
   q->n_hidden = cfg->n_hidden; q->out_map = cfg->out_map;
   for (int l = 0; l < 2; ++l) q->width[l] = l < cfg->n_hidden ? cfg->width[l] : 0;
-  const std::vector<double> blob = pack_policy(cfg);
   q->blob_doubles = blob.size();
   hipError_t e = hipGetDevice(&q->device);
   if (e == hipSuccess) e = hipMalloc((void**)&q->dP, sizeof(double) * blob.size());
@@ -1711,6 +1759,15 @@ int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) {
   return PCG_OK;
 }
 
+int pcg_policy_create(pcg_policy** out, const pcg_policy_cfg* cfg) { return policy_create(out, cfg, PCG_POL_F64); }
+int pcg_policy_create_f32(pcg_policy** out, const pcg_policy_cfg* cfg) { return policy_create(out, cfg, PCG_POL_F32); }
+
+int pcg_policy_dtype(const pcg_policy* q) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC) return PCG_E_PLAN;
+  return q->dtype;
+}
+
 int pcg_policy_update(pcg_policy* q, const pcg_policy_cfg* cfg) {
   if (!q) return PCG_E_NULL;
   if (q->magic != POLICY_MAGIC) return PCG_E_PLAN;
@@ -1718,7 +1775,9 @@ int pcg_policy_update(pcg_policy* q, const pcg_policy_cfg* cfg) {
   if (cfg->n_in != q->n_in || cfg->n_out != q->n_out || cfg->n_hidden != q->n_hidden) return PCG_E_DIM;
   for (int l = 0; l < cfg->n_hidden; ++l)
     if (cfg->width[l] != q->width[l]) return PCG_E_DIM;
-  const std::vector<double> blob = pack_policy(cfg);
+  int prc = PCG_OK;
+  const std::vector<double> blob = q->dtype == PCG_POL_F32 ? pack_policy_f32(cfg, &prc) : pack_policy(cfg);
+  PCG_TRY(prc);
   if (blob.size() != q->blob_doubles) return PCG_E_DIM;  // (cannot happen: the block's size is a function of the shape)
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -1787,8 +1846,8 @@ static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return 
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
 
 template <class Fn>
-static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2], StepArgs* a,
-                            Fn* fn) {
+static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2],
+                            Fn (Kernels::*table_f32)[2], StepArgs* a, Fn* fn) {
   PCG_TRY(fill_args(p, io, a));
   if (!q) return PCG_E_NULL;
   if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
@@ -1798,7 +1857,7 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   const int ls = lean_scheme(p->integrator_id);
   if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
   // (a run-time compiled plan has no ahead-of-time kernel: closed_loop_launch takes its own module's)
-  *fn = p->jit_fn[0] ? nullptr : (kernels(p->kid).*table)[ls];
+  *fn = p->jit_fn[0] ? nullptr : (kernels(p->kid).*(q->dtype == PCG_POL_F32 ? table_f32 : table))[ls];
   if (!*fn && !p->jit_fn[0]) return PCG_E_UNSUPPORTED;
   if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
   return PCG_OK;
@@ -1806,7 +1865,7 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
 
 template <class Fn, class HeadArgs>
 static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, Fn fn, const HeadArgs& head, const ClosedLoopRun& r,
-                              std::initializer_list<SeqRec> head_recs, void* stream) {
+                              std::initializer_list<SeqRec> head_recs, int f32, int late_status, void* stream) {
   const DevConst& c = p->hc;
   if (r.T < 1 || r.t0 < 0 || (int64_t)r.t0 + (int64_t)r.T > 0x7fffffffLL) return PCG_E_VALUE;
   if (io->B == 0) return PCG_OK;
@@ -1816,6 +1875,10 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
   if (r.obs_seq && r.obs_cs < io->B) return PCG_E_DIM;
   for (const SeqRec& h : head_recs)
     if (h.seq && h.comp_stride < io->B) return PCG_E_DIM;
+  // what the float32 form adds, after every other check: networks of two dtypes in one call (late_status), and a plan with
+  // run-time compiled code, whose closed-loop module carries the fp64 kernels alone -- nothing compiled, nothing launched
+  if (late_status != PCG_OK) return late_status;
+  if (f32 && p->jit_fn[0]) return PCG_E_UNSUPPORTED;
   a.t_scalar = r.t0; a.seed = r.seed; a.T = r.T;
   a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
   a.obs_seq = r.obs_seq; a.rew_seq = r.rew_seq;
@@ -1846,13 +1909,13 @@ int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, 
                        uint64_t seed, void* stream) {
   StepArgs a;
   PolFn fn;
-  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_policy, &a, &fn));
+  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_policy, &Kernels::roll_policy_f32, &a, &fn));
   PolicyArgs pa;
   pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
   pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
   pa.record_next = record_next_action ? 1 : 0;
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, stream);
+  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, q->dtype == PCG_POL_F32, PCG_OK, stream);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {
@@ -1884,7 +1947,7 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
                       int32_t record_next_action, uint64_t seed, void* stream) {
   StepArgs a;
   ActFn fn;
-  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_actor, &a, &fn));
+  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_actor, &Kernels::roll_actor_f32, &a, &fn));
   const DevConst& c = p->hc;
   if (v) {
     if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
@@ -1908,7 +1971,10 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
   aa.c0 = pcg_actor_logp_const(sigma, c.na);
   aa.record_next = record_next_action ? 1 : 0;
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, stream);
+  // (one kernel evaluates both networks: an actor and a critic of different dtypes are refused, after every other check)
+  const int mixed = (v && v->dtype != q->dtype) ? PCG_E_UNSUPPORTED : PCG_OK;
+  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, q->dtype == PCG_POL_F32,
+                            mixed, stream);
 }
 
 int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {

@@ -1151,6 +1151,10 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 // (also under hipRTC: a plan's second run-time compiled module instantiates the two closed-loop kernels, pcg_abi.hip jit_closed_loop)
 #include "pcg_rollout_policy.hpp"
 #include "pcg_rollout_actor.hpp"
+#ifndef __HIPCC_RTC__
+// (ahead-of-time only: a plan's run-time compiled closed-loop module carries the fp64 kernels alone)
+#include "pcg_rollout_policy_f32.hpp"
+#endif
 namespace pcg {
 
 using StepFn = void (*)(const StepArgs);
@@ -1207,6 +1211,8 @@ struct Kernels {
   StepFn roll_hot;                   // second pass of the barrier-free rollout of a PCG_INT_T5G plan (models with a guard)
   PolFn roll_policy[2];              // closed-loop fused rollout with an on-device MLP policy [lean_scheme(integrator)]
   ActFn roll_actor[2];               // ... with a Gaussian actor (sampled action, log-prob) and an optional critic
+  PolFn roll_policy_f32[2];          // the same two with the networks evaluated in float32 (pcg_rollout_policy_f32.hpp)
+  ActFn roll_actor_f32[2];
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1271,6 +1277,10 @@ Kernels make_kernels() {
   k.roll_policy[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel<M, PCG_INT_CV8>;
   k.roll_actor[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel<M, PCG_INT_RK4>;
   k.roll_actor[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel<M, PCG_INT_CV8>;
+  k.roll_policy_f32[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel_f32<M, PCG_INT_RK4>;
+  k.roll_policy_f32[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel_f32<M, PCG_INT_CV8>;
+  k.roll_actor_f32[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel_f32<M, PCG_INT_RK4>;
+  k.roll_actor_f32[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel_f32<M, PCG_INT_CV8>;
   // Tsit5 (the reference's jax method): general kernel, both counter modes, and the integration hook
   k.step[PCG_INT_TSIT5][0][0][0] = k.step[PCG_INT_TSIT5][0][0][1] = step_kernel<M, PCG_INT_TSIT5, false, false, true>;
   k.step[PCG_INT_TSIT5][1][0][0] = k.step[PCG_INT_TSIT5][1][0][1] = step_kernel<M, PCG_INT_TSIT5, true, false, true>;

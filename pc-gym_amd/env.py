@@ -319,7 +319,9 @@ class VecEnv:
         now instead of at the first ``rollout_policy`` / ``rollout_actor`` / fused ``collect_*`` call: a caller who records
         those calls into a graph (``torch.cuda.graph``) has to, since a module cannot be loaded while a stream is being
         captured.  Does nothing on a built-in plan; a second call does nothing; a run-time compiled plan the closed-loop
-        kernels do not take (constraints, integrators other than rk4 / cv8) raises PcgError."""
+        kernels do not take (constraints, integrators other than rk4 / cv8) raises PcgError.  The module carries the float64
+        kernels only: a float32 policy (``MLPPolicy(..., dtype="float32")``) is refused on such a plan whether or not this
+        was called, and ``collect_rollouts`` / ``collect_onpolicy`` step it with the float32 callable."""
         with _torch().cuda.device(self.device):
             _lib.check(self._lib.pcg_plan_prepare_closed_loop(self._plan), "pcg_plan_prepare_closed_loop")
         return self
@@ -332,7 +334,9 @@ class VecEnv:
         as the caller would have passed them to step(); with ``record_next_action`` row T is the policy's proposal for
         the observation after the last step, not applied.  Plans the kernel does not take (constraints, per-env
         parameters, integrators other than rk4 / cv8) raise PcgError: loop over step() for those.  A user model or a
-        plan with a reward expression compiles its closed-loop kernels at the first such call (``prepare_closed_loop``)."""
+        plan with a reward expression compiles its closed-loop kernels at the first such call (``prepare_closed_loop``).
+        The policy's dtype decides the kernel: a float32 policy is evaluated in float32 (every recorded output is a float32
+        value; built-in plans only), the env arithmetic is fp64 either way."""
         if self.per_env_t:
             raise ValueError("rollout_policy() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)
@@ -355,7 +359,9 @@ class VecEnv:
         the critic's value of the same observation.  Returns a dict of the recorded arrays (None where not asked for, "val"
         None without a critic): "a" / "u" (T [+1], na, B), "logp" / "val" (T [+1], B), "obs" (T, Nobs, B), "rew" (T, B).  With
         ``record_next_action`` row T holds the four quantities for the observation after the last step (drawn at counter
-        t + T, not applied): its value is the bootstrap value.  Plans / networks the kernel does not take raise PcgError."""
+        t + T, not applied): its value is the bootstrap value.  Plans / networks the kernel does not take raise PcgError.
+        Float32 networks (actor and critic of one dtype) are evaluated in float32: ``mu`` and the value are widened float32
+        results, the sample, the map and the log-probability are fp64 as for float64 networks."""
         if self.per_env_t:
             raise ValueError("rollout_actor() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)

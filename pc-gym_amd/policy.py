@@ -1,4 +1,4 @@
-"""Declarative policies: a small fp64 multi-layer perceptron that the engine can evaluate INSIDE the rollout kernel.
+"""Declarative policies: a small fp64 (or, by choice, float32) multi-layer perceptron that the engine can evaluate INSIDE the rollout kernel.
 
 The reference evaluates ``policy.predict(obs)`` on the host between two ``env.step`` calls
 (src/pcgym/policy_evaluation.py:86-128); its policies are stable-baselines3 ``MlpPolicy`` networks: a few ``Linear``
@@ -25,6 +25,20 @@ from . import _lib
 
 _ACT = {"tanh": abi.PCG_ACT_TANH, "relu": abi.PCG_ACT_RELU}
 _OUT = {"none": abi.PCG_POL_NONE, "clip": abi.PCG_POL_CLIP, "tanh": abi.PCG_POL_TANH}
+_DTYPE = {"float64": np.float64, "float32": np.float32}
+
+
+def _as(values, np_dtype, what):
+    """contiguous array of `np_dtype`, rounded to nearest; a finite value that overflows float32 raises ValueError"""
+    v64 = np.asarray(values, dtype=np.float64)
+    if np_dtype is np.float64:
+        return np.ascontiguousarray(v64) if v64.ndim else v64
+    with np.errstate(over="ignore"):
+        v = v64.astype(np.float32)
+    v = np.ascontiguousarray(v) if v.ndim else v
+    if np.any(np.isinf(v) & np.isfinite(v64)):
+        raise ValueError(f"{what}: a value overflows float32")
+    return v
 
 
 def _torch():
@@ -35,15 +49,23 @@ def _torch():
 
 class MLPPolicy:
     """weights[l] : (n_next, n_prev) array (``torch.nn.Linear.weight`` layout), biases[l] : (n_next,);
-    activation : "tanh" | "relu" between layers; out_map : "none" | "clip" (to [out_low, out_high]) | "tanh"."""
+    activation : "tanh" | "relu" between layers; out_map : "none" | "clip" (to [out_low, out_high]) | "tanh".
+    dtype : "float64" (default) | "float32".  Under "float32" weights, biases and the clip box are stored as ``np.float32``
+    (rounded to nearest; an overflow raises ValueError), the callable computes in torch float32 on ``obs.to(float32)`` and
+    returns float64 tensors (exact widening), and the device form is ``pcg_policy_create_f32``: the network is evaluated in
+    float32 inside the kernel, as stable-baselines3 evaluates the module it trained."""
 
-    def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0):
+    def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype="float64"):
+        if dtype not in _DTYPE:
+            raise ValueError(f"dtype must be one of {sorted(_DTYPE)}, not {dtype!r}")
+        self.dtype = dtype
+        npd = _DTYPE[dtype]
         if activation not in _ACT:
             raise ValueError(f"activation must be one of {sorted(_ACT)}, not {activation!r}")
         if out_map not in _OUT:
             raise ValueError(f"out_map must be one of {sorted(_OUT)}, not {out_map!r}")
-        self.weights = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)) for w in weights]
-        self.biases = [np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1)) for b in biases]
+        self.weights = [_as(w, npd, "weights") for w in weights]
+        self.biases = [_as(b, npd, "biases").reshape(-1) for b in biases]
         if not self.weights or len(self.weights) != len(self.biases):
             raise ValueError("one bias vector per weight matrix, at least one layer")
         for l, (w, b) in enumerate(zip(self.weights, self.biases)):
@@ -52,7 +74,7 @@ class MLPPolicy:
             if l and w.shape[1] != self.weights[l - 1].shape[0]:
                 raise ValueError(f"layer {l}: {w.shape[1]} inputs after a layer of {self.weights[l - 1].shape[0]} units")
         self.activation, self.out_map = activation, out_map
-        self.out_low, self.out_high = float(out_low), float(out_high)
+        self.out_low, self.out_high = float(_as(out_low, npd, "out_low")), float(_as(out_high, npd, "out_high"))
         self.n_in, self.n_out = int(self.weights[0].shape[1]), int(self.weights[-1].shape[0])
         self.n_hidden = len(self.weights) - 1
         self._tensors = {}   # device -> ([W], [b]) torch tensors
@@ -68,12 +90,12 @@ class MLPPolicy:
             self._tensors[key] = ([torch.as_tensor(w, device=obs.device) for w in self.weights],
                                   [torch.as_tensor(b, device=obs.device) for b in self.biases])
         Ws, bs = self._tensors[key]
-        h = obs.to(torch.float64)
+        h = obs.to(torch.float32 if self.dtype == "float32" else torch.float64)
         for l, (w, b) in enumerate(zip(Ws, bs)):
             h = torch.addmm(b, h, w.t())
             if l < self.n_hidden:
                 h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
-        return h
+        return h.to(torch.float64)
 
     def map(self, h):
         """the output map alone: what turns ``raw(obs)`` into the policy's output"""
@@ -81,7 +103,8 @@ class MLPPolicy:
         if self.out_map == "clip":
             h = torch.clamp(h, self.out_low, self.out_high)
         elif self.out_map == "tanh":
-            h = torch.tanh(h)
+            # (a float32 policy's raw output is a float32 value: tanh in float32 before the widening, as in the kernel)
+            h = torch.tanh(h.to(torch.float32)).to(torch.float64) if self.dtype == "float32" else torch.tanh(h)
         return h
 
     def __call__(self, obs):
@@ -91,8 +114,8 @@ class MLPPolicy:
         """New weights of IDENTICAL shape, in place: the host arrays, the cached torch tensors and every live device handle
         (``pcg_policy_update``: the device block is rewritten, nothing is allocated or freed).  A shape change raises
         ValueError and leaves the policy as it was."""
-        ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)) for w in weights]
-        bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1)) for b in biases]
+        ws = [_as(w, _DTYPE[self.dtype], "weights") for w in weights]
+        bs = [_as(b, _DTYPE[self.dtype], "biases").reshape(-1) for b in biases]
         if [w.shape for w in ws] != [w.shape for w in self.weights] or [b.shape for b in bs] != [b.shape for b in self.biases]:
             raise ValueError(f"update_ keeps the shape: {[w.shape for w in self.weights]}, not {[w.shape for w in ws]}")
         old = (self.weights, self.biases)
@@ -108,10 +131,11 @@ class MLPPolicy:
         return self
 
     @classmethod
-    def from_torch(cls, module, out_map=None, out_low=-1.0, out_high=1.0):
+    def from_torch(cls, module, out_map=None, out_low=-1.0, out_high=1.0, dtype=None):
         """From an ``nn.Sequential`` of ``Linear`` layers with ``Tanh`` or ``ReLU`` between them (one kind).  A ``Tanh``
         after the last ``Linear`` becomes ``out_map="tanh"``; otherwise ``out_map`` defaults to "clip".  Anything else in
-        the module raises ValueError."""
+        the module raises ValueError.  ``dtype=None``: a float64 policy (every parameter widened); ``dtype="float32"``: a
+        float32 policy, which holds a float32 module's parameters bit for bit."""
         nn = _torch().nn
         if not isinstance(module, nn.Sequential):
             raise ValueError(f"from_torch takes an nn.Sequential, not {type(module).__name__}")
@@ -145,7 +169,7 @@ class MLPPolicy:
                 raise ValueError(f"the module ends in Tanh: out_map={out_map!r} contradicts it")
             out_map = "tanh"
         return cls(weights, biases, activation=acts[0] if acts else "tanh", out_map=out_map or "clip",
-                   out_low=out_low, out_high=out_high)
+                   out_low=out_low, out_high=out_high, dtype=dtype or "float64")
 
     # ---- the C ABI side ------------------------------------------------------------------------------------------------
     def to_cfg(self):
@@ -157,10 +181,14 @@ class MLPPolicy:
         cfg.activation, cfg.out_map = _ACT[self.activation], _OUT[self.out_map]
         cfg.out_low, cfg.out_high = self.out_low, self.out_high
         pd = C.POINTER(C.c_double)
-        for l in range(min(len(self.weights), 3)):
-            cfg.W[l] = self.weights[l].ctypes.data_as(pd)
-            cfg.b[l] = self.biases[l].ctypes.data_as(pd)
-        return cfg, [self.weights, self.biases]
+        # (pcg_policy_cfg carries doubles: a float32 policy passes exact widenings, which pcg_policy_create_f32 rounds back)
+        ws, bs = self.weights, self.biases
+        if self.dtype == "float32":
+            ws, bs = [w.astype(np.float64) for w in ws], [b.astype(np.float64) for b in bs]
+        for l in range(min(len(ws), 3)):
+            cfg.W[l] = ws[l].ctypes.data_as(pd)
+            cfg.b[l] = bs[l].ctypes.data_as(pd)
+        return cfg, [ws, bs]
 
     def validate(self):
         """status of pcg_policy_validate (host only: no GPU needed); 0 = the engine can evaluate this policy on the device"""
@@ -176,7 +204,8 @@ class MLPPolicy:
             cfg, keep = self.to_cfg()
             h = C.c_void_p()
             with torch.cuda.device(idx):
-                _lib.check(_lib.load().pcg_policy_create(C.byref(h), C.byref(cfg)), "pcg_policy_create")
+                create = "pcg_policy_create_f32" if self.dtype == "float32" else "pcg_policy_create"
+                _lib.check(getattr(_lib.load(), create)(C.byref(h), C.byref(cfg)), create)
             self._handles[idx] = h
         return self._handles[idx]
 
@@ -195,9 +224,17 @@ class MLPPolicy:
 def fused_policy_ok(spec, policy):
     """the plans pcg_rollout_policy takes (include/pcgym_hip.h): fixed-step RK4 / CV8, no constraint rows (a constraint
     expression is ``ncon`` rows too), no per-env parameters -- user models and reward expressions included, which run the
-    kernel from their plan's own run-time compiled module -- and a policy of the plan's sizes that the device form can hold"""
+    kernel from their plan's own run-time compiled module -- and a policy of the plan's sizes that the device form can hold.
+    A float32 policy qualifies on the built-in plans only: the run-time compiled module carries the float64 kernels alone,
+    and ``collect_*`` step such a plan with the float32 callable instead."""
     return (isinstance(policy, MLPPolicy) and spec.integrator in ("rk4", "cv8") and not spec.ncon and not spec.nunc
-            and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
+            and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0
+            and not (policy.dtype == "float32" and _runtime_compiled(spec)))
+
+
+def _runtime_compiled(spec):
+    """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
+    return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)
 
 
 def _module_arrays(module):
@@ -219,7 +256,8 @@ class GaussianActorCritic:
 
     ``log_prob`` is the log-density of the UNMAPPED sample ``u`` under N(mu, sigma^2) -- stable-baselines3 PPO's meaning: the
     env clips, the buffer keeps ``u``.  The torch methods work in fp64 on the observation's device (CPU included), with the
-    kernel's formulas and summation order (components ascending)."""
+    kernel's formulas and summation order (components ascending).  With float32 networks (actor and critic of one dtype)
+    ``mean`` and ``value`` are the widened float32 results; ``sample``, ``log_prob`` and ``log_prob_z`` stay fp64."""
 
     def __init__(self, actor, log_std, critic=None):
         if not isinstance(actor, MLPPolicy):
@@ -234,6 +272,8 @@ class GaussianActorCritic:
                 raise ValueError(f"the critic has one output and no output map (n_out={critic.n_out}, out_map={critic.out_map!r})")
             if critic.n_in != actor.n_in:
                 raise ValueError(f"the critic reads {critic.n_in} inputs, the actor {actor.n_in}")
+            if critic.dtype != actor.dtype:
+                raise ValueError(f"actor and critic must have one dtype ({actor.dtype} / {critic.dtype}): one kernel evaluates both")
         self.actor, self.critic = actor, critic
         self.n_in, self.n_out = actor.n_in, actor.n_out
         self._set_log_std(log_std)
@@ -296,11 +336,12 @@ class GaussianActorCritic:
         return self.critic.raw(obs)[:, 0]
 
     @classmethod
-    def from_torch(cls, actor_seq, log_std, critic_seq=None, out_map=None, out_low=-1.0, out_high=1.0):
+    def from_torch(cls, actor_seq, log_std, critic_seq=None, out_map=None, out_low=-1.0, out_high=1.0, dtype=None):
         """From the ``nn.Sequential`` of the actor (MLPPolicy.from_torch's forms; ``out_map`` defaults to "clip"), its
-        ``log_std`` (tensor, Parameter or array) and, optionally, the ``nn.Sequential`` of the value network."""
-        actor = MLPPolicy.from_torch(actor_seq, out_map=out_map, out_low=out_low, out_high=out_high)
-        critic = MLPPolicy.from_torch(critic_seq, out_map="none") if critic_seq is not None else None
+        ``log_std`` (tensor, Parameter or array) and, optionally, the ``nn.Sequential`` of the value network; ``dtype`` as in
+        MLPPolicy.from_torch, for both networks."""
+        actor = MLPPolicy.from_torch(actor_seq, out_map=out_map, out_low=out_low, out_high=out_high, dtype=dtype)
+        critic = MLPPolicy.from_torch(critic_seq, out_map="none", dtype=dtype) if critic_seq is not None else None
         return cls(actor, log_std, critic)
 
     def update_(self, actor=None, log_std=None, critic=None):

@@ -3,7 +3,7 @@
 log-probability and critic evaluated in the rollout kernel) against the per-step route with the same networks, and against
 the deterministic fused call (pcg_rollout_policy) with the same actor.
 
-    python tools/actor_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--out FILE]
+    python tools/actor_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--dtype float32] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s).  Four routes alternate inside one process
 (`reps` rounds after one warm-up round); times are device-event times of whole episodes (reset included), the figure
@@ -13,6 +13,8 @@ compared is the median:
     c   collect_rollouts(env, policy=ac.actor)   the deterministic fused call, same actor
     a0  reset + VecEnv.rollout_actor without a critic (samples, log-probabilities, observations, rewards recorded)
 The condition: a is not slower than b for any shape (collect_onpolicy takes the fused call wherever the plan qualifies).
+With --dtype float32 three routes alternate instead: a32 = collect_onpolicy fused with float32 networks, a64 = the same with
+float64 networks of the same (rounded) weights, b32 = the per-step route of the float32 networks.
 """
 import argparse
 import os
@@ -24,19 +26,59 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tools")]
 
-from policy_rollout_bench import SHAPES, make_policy, policy_fmas  # noqa: E402
+from policy_rollout_bench import SHAPES, make_policy, policy_fmas, widened  # noqa: E402
 
 
-def make_ac(spec, hidden, critic=True, seed=17):
+def make_ac(spec, hidden, critic=True, seed=17, dtype="float64"):
     """policy_rollout_bench's actor, sigma = exp(-1.5) (0.22 of the normalised action half width), a critic of the same shape"""
     from pcgym_amd import GaussianActorCritic, MLPPolicy
 
-    actor = make_policy(spec, hidden, seed)
+    actor = make_policy(spec, hidden, seed, dtype=dtype)
     cr = None
     if critic:
-        c = make_policy(spec, hidden, seed + 100)
-        cr = MLPPolicy(c.weights[:-1] + [c.weights[-1][:1]], c.biases[:-1] + [c.biases[-1][:1]], activation="tanh", out_map="none")
+        c = make_policy(spec, hidden, seed + 100, dtype=dtype)
+        cr = MLPPolicy(c.weights[:-1] + [c.weights[-1][:1]], c.biases[:-1] + [c.biases[-1][:1]], activation="tanh", out_map="none", dtype=dtype)
     return GaussianActorCritic(actor, np.full(spec.na, -1.5), cr)
+
+
+def f32_rows(a, p, VecEnv, collect_onpolicy, torch):
+    from pcgym_amd import GaussianActorCritic
+
+    lines = ["# float32 networks: a32 = collect_onpolicy fused float32, a64 = fused float64 on the same rounded weights (the baseline), "
+             "b32 = per-step route of the float32 networks"]
+    for name in a.shapes.split(","):
+        envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("a32", "a64", "b32")}
+        spec = envs["a32"].spec
+        ac = make_ac(spec, SHAPES[name], dtype="float32")
+        ac64 = GaussianActorCritic(widened(ac.actor), ac.log_std, widened(ac.critic))
+        steps = spec.N - 1
+        routes = {"a32": lambda: collect_onpolicy(envs["a32"], ac), "a64": lambda: collect_onpolicy(envs["a64"], ac64),
+                  "b32": lambda: collect_onpolicy(envs["b32"], ac, fused=False)}
+        times = {k: [] for k in routes}
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        verdict = "float32 faster than float64" if med["a32"] < med["a64"] else "FLOAT32 NOT FASTER THAN FLOAT64"
+        lines.append(f"{name:7s} a32 {us['a32']:8.2f}  a64 {us['a64']:8.2f}  b32 {us['b32']:8.2f} us/step   a64 / a32 = {med['a64'] / med['a32']:.2f}   "
+                     f"b32 / a32 = {med['b32'] / med['a32']:.2f}   {a.B * steps / med['a32'] / 1e-3:.3e} env-steps/s fused float32   "
+                     f"FMAs per env step: actor {policy_fmas(ac.actor)}, critic {policy_fmas(ac.critic)}   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        ac.close(), ac64.close()
+        del envs
+        torch.cuda.empty_cache()
+    return lines
 
 
 def main():
@@ -44,6 +86,7 @@ def main():
     ap.add_argument("--B", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="affine,1x16,2x64")
+    ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -59,7 +102,9 @@ def main():
              "# a = collect_onpolicy fused (actor + critic), b = its per-step route, c = deterministic pcg_rollout_policy "
              "(same actor), a0 = fused without a critic"]
     p = bench.workload_params()
-    for name in a.shapes.split(","):
+    if a.dtype == "float32":
+        lines += f32_rows(a, p, VecEnv, collect_onpolicy, torch)
+    for name in ([] if a.dtype == "float32" else a.shapes.split(",")):
         envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("a", "b", "c", "a0")}
         spec = envs["a"].spec
         ac, ac0 = make_ac(spec, SHAPES[name]), make_ac(spec, SHAPES[name], critic=False)

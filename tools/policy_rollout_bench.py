@@ -3,12 +3,14 @@
 against the per-step route (collect_rollouts with the same policy as a torch callable: one pcg_step launch and one torch
 evaluation per step, obs and a through HBM) -- the reference's policy_eval.rollout loop, policy_evaluation.py:71-130.
 
-    python tools/policy_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--out FILE]
+    python tools/policy_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--dtype float32] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s), both routes through collect_rollouts, so
 both produce the reference's x (Nx, N, B) / u (na, N, B) / r (1, N, B) arrays.  The two routes alternate inside one
 process (`reps` pairs after one warm-up pair each); times are device-event times of whole episodes, the figure compared is
 the median.  The 2 x 64 policy is also reported as a share of the fp64 vector peak (FMAs of the policy alone).
+With --dtype float32 three routes alternate: the float32 fused call (rollout_policy_kernel_f32), the float64 fused call on the
+same (float32-rounded) weights, and the per-step route with the float32 callable.
 """
 import argparse
 import os
@@ -24,7 +26,7 @@ SHAPES = {"affine": (), "1x16": (16,), "2x64": (64, 64)}
 FP64_VECTOR_PEAK = 78.6e12  # MI355X, FLOP/s (spec: half the fp32 vector rate)
 
 
-def make_policy(spec, hidden, seed=17):
+def make_policy(spec, hidden, seed=17, dtype="float64"):
     """fixed-seed weights on the normalised observation / action boxes: unsaturated units, outputs mostly inside [-1, 1]"""
     from pcgym_amd import MLPPolicy
 
@@ -33,11 +35,66 @@ def make_policy(spec, hidden, seed=17):
     Ws = [rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l]) for l in range(len(dims) - 1)]
     bs = [0.2 * rng.standard_normal(dims[l + 1]) for l in range(len(dims) - 1)]
     Ws[-1] *= 0.8
+    if dtype == "float32":  # (both dtypes of a comparison hold the same, float32-rounded, weights)
+        Ws, bs = [w.astype(np.float32) for w in Ws], [b.astype(np.float32) for b in bs]
+        return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype="float32")
     return MLPPolicy(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+
+
+def widened(pol):
+    """the float64 policy with a float32 policy's weights"""
+    from pcgym_amd import MLPPolicy
+
+    return MLPPolicy(pol.weights, pol.biases, activation=pol.activation, out_map=pol.out_map, out_low=pol.out_low, out_high=pol.out_high)
 
 
 def policy_fmas(pol):
     return sum(int(w.size) for w in pol.weights)
+
+
+def f32_rows(a, p, VecEnv, collect_rollouts, torch):
+    """the float32 comparison: fused32 / fused64 / per_step32 interleaved, us per step"""
+    lines = ["# float32 policy: f32 = fused float32 call, f64 = fused float64 call on the same rounded weights (the baseline), "
+             "ps32 = per-step route with the float32 callable"]
+    for name in a.shapes.split(","):
+        envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("f32", "f64", "ps32")}
+        spec = envs["f32"].spec
+        pol = make_policy(spec, SHAPES[name], dtype="float32")
+        pol64 = widened(pol)
+        steps = spec.N - 1
+        routes = {"f32": lambda: collect_rollouts(envs["f32"], policy=pol), "f64": lambda: collect_rollouts(envs["f64"], policy=pol64),
+                  "ps32": lambda: collect_rollouts(envs["ps32"], policy=lambda o: pol(o))}
+        times = {k: [] for k in routes}
+        gap = float("nan")
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            u = {}
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                if rep == 0 and k != "ps32":
+                    u[k] = d["u"][:, 0].clone()  # the first action: the same observation on both routes
+                del d
+            if rep == 0:
+                gap = float((u["f32"] - u["f64"]).abs().max())
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        verdict = "float32 faster than float64" if med["f32"] < med["f64"] else "FLOAT32 NOT FASTER THAN FLOAT64"
+        lines.append(f"{name:7s} f32 {us['f32']:8.2f}  f64 {us['f64']:8.2f}  ps32 {us['ps32']:8.2f} us/step   f64 / f32 = {med['f64'] / med['f32']:.2f}   "
+                     f"ps32 / f32 = {med['ps32'] / med['f32']:.2f}   {a.B * steps / med['f32'] / 1e-3:.3e} env-steps/s fused float32   "
+                     f"policy FMAs per env step {policy_fmas(pol)}   first action f32 vs f64: max |diff| {gap:.2e}   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        pol.close(), pol64.close()
+        del envs
+        torch.cuda.empty_cache()
+    return lines
 
 
 def main():
@@ -45,6 +102,7 @@ def main():
     ap.add_argument("--B", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="affine,1x16,2x64")
+    ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -58,7 +116,9 @@ def main():
              f"({os.path.relpath(_lib.LIB_PATH, ROOT)})  {torch.cuda.get_device_name(0)}",
              "# cstr, RK4 x 1, N = 60: one episode = 59 closed-loop steps; ms per episode, median of the interleaved repeats"]
     p = bench.workload_params()
-    for name in a.shapes.split(","):
+    if a.dtype == "float32":
+        lines += f32_rows(a, p, VecEnv, collect_rollouts, torch)
+    for name in ([] if a.dtype == "float32" else a.shapes.split(",")):
         e_f, e_s = VecEnv(dict(p), n_envs=a.B, seed=1), VecEnv(dict(p), n_envs=a.B, seed=1)
         spec = e_f.spec
         pol = make_policy(spec, SHAPES[name])
