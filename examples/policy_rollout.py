@@ -63,6 +63,7 @@ def main():
     policy.close()
     float32_leg(net, B)
     actor_critic(net, B)
+    constrained(net, B)
 
 
 def float32_leg(net, B):
@@ -115,6 +116,38 @@ def actor_critic(actor_net, B):
     d = collect_onpolicy(env, ac)
     print(f"after update_: sigma {ac.sigma[0]:.4f}, mean logp {d['logp'].mean().item():.3f}")
     env.close(), ac.close()
+
+
+def constrained(actor_net, B):
+    """the same envs with constraint rows (a temperature band, -1000 penalty while outside): the fused calls record every
+    step's rows and violation flags -- `g` of collect_rollouts in the reference's axis order, `g` / `g_pre` / `viol` of
+    collect_onpolicy(record_cons=True): a cost signal or a mask for a constrained trainer.  An env that violates keeps
+    stepping; mask what follows from `viol`."""
+    # (reference_compat=False: the rows read the physical state; the reference hands its constraint callable a state it has
+    # "de-normalised" a second time when normalise_o is set -- quirk Q3 -- and a band in kelvin means nothing there)
+    p = dict(copy.deepcopy(env_params), r_penalty=True, done_on_cons_vio=False, reference_compat=False,
+             constraints={"A": np.array([[0.0, 1.0, 0.0, 0.0], [0.0, -1.0, 0.0, 0.0]]), "b": np.array([332.0, -321.0])})
+    policy = MLPPolicy.from_torch(actor_net, out_map="clip", out_low=-1.0, out_high=1.0)
+    for name, pol in (("per step", lambda obs: policy(obs)), ("fused", policy)):
+        env = make_vec_env(p, n_envs=B, seed=0)
+        collect_rollouts(env, policy=pol)  # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        d = collect_rollouts(env, policy=pol)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"constrained, {name:8s}: {dt * 1e3:7.2f} ms per episode  g {tuple(d['g'].shape)}  "
+              f"entries violated {(d['g'][:, 1:] > 0).any(dim=0).double().mean().item():.3f}  mean return {d['r'].sum(dim=1).mean().item():.1f}")
+        env.close()
+    critic_net = torch.nn.Sequential(torch.nn.Linear(3, 16), torch.nn.Tanh(), torch.nn.Linear(16, 1)).double()
+    ac = GaussianActorCritic.from_torch(actor_net, torch.full((1,), -1.0, dtype=torch.float64), critic_net, out_map="clip",
+                                        out_low=-1.0, out_high=1.0)
+    env = make_vec_env(p, n_envs=B, seed=0)
+    d = collect_onpolicy(env, ac, record_cons=True)
+    first = torch.where(d["viol"].any(dim=0), d["viol"].double().argmax(dim=0), d["viol"].shape[0])
+    print(f"constrained actor-critic: g {tuple(d['g'].shape)} g_pre {tuple(d['g_pre'].shape)} viol {tuple(d['viol'].shape)}  "
+          f"envs that violate at some step {d['viol'].any(dim=0).double().mean().item():.3f}, first at step {first.double().mean().item():.1f} on average")
+    env.close(), ac.close(), policy.close()
 
 
 if __name__ == "__main__":

@@ -600,6 +600,48 @@ PCG_API int pcg_rollout_actor(pcg_plan* plan, const pcg_buffers* io, const pcg_p
                               double* logp_out, int64_t logp_step_stride, double* value_out, int64_t value_step_stride,
                               double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                               int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
+/* The two closed-loop calls on plans WITH constraint rows, recording the rows (additive under ABI 16; kernels:
+ * csrc/pcg_rollout_cons.hpp).  Every argument of pcg_rollout_policy / pcg_rollout_actor up to record_next_action keeps its
+ * meaning, the loop, the networks' arithmetic and the Philox keys are theirs.  Added per step s (counter t0 + s):
+ *   - g_seq[s * g_step_stride + r * g_comp_stride + e] receives row r of the ncon affine rows g = A.[x|SP|d|u] - b after
+ *     the step; viol_seq[s * viol_step_stride + e] the byte "any row > 0".  Either may be NULL.  Step-major
+ *     ([T][ncon][B]-like) or component-major ([ncon][T][B]-like, the reference's cons_info order) rows, as obs_seq;
+ *   - after the last step io->g and io->viol (where given) hold that step's rows and flag and io->done its done flag,
+ *     PCG_F_DONE_ON_CONS included: what pcg_step leaves.  At counter 0 the pre-step check (pcgym.py:414-420) writes
+ *     io->g_pre (where given) and enters `done`; a call with t0 > 0 leaves io->g_pre alone;
+ *   - the flag feeds the -1000 penalty (r_penalty), the box excess of the declarative tracking reward and `done`.
+ * After `done`: an env whose done flag is set mid-episode (done_on_cons_vio) KEEPS STEPPING, exactly as a loop over pcg_step
+ * on a lock-stepped batch does, which never resets single envs; mask what follows a violation from viol_seq.
+ * Summation order.  g > 0 decides the penalty and `done`, so a row's last bit matters.  The rows are the bits pcg_step
+ * leaves in io->g on the same plan and buffers: where pcg_step takes the feature-masked kernel (PCG_INT_RK4 plans of the
+ * small models on an even, 16-byte-aligned batch) g = -b, + the SP slots, + the disturbance slots, + the states ascending,
+ * + the actions, + the model disturbance inputs; everywhere else the states come first, then SP slots, disturbance slots,
+ * actions, model disturbance inputs.  One fused multiply-add per term.
+ * Plans: those of pcg_rollout_policy with ncon > 0 and affine rows -- lock-stepped, no per-env parameters, PCG_INT_RK4 /
+ * PCG_INT_CV8, built-in.  PCG_E_UNSUPPORTED, before anything is launched: ncon == 0 (use pcg_rollout_policy /
+ * pcg_rollout_actor), a plan with run-time compiled code (PCG_MODEL_USER, user_reward_src, user_cons_src: its closed-loop
+ * module carries the two unconstrained kernels only), io->t != NULL, nunc > 0, any other integrator, a float32 policy,
+ * actor or critic.  Every other status as in pcg_rollout_policy / pcg_rollout_actor and in their order (policy handle,
+ * sizes, critic, sigma, T / t0, NULL buffers, strides); PCG_E_DIM besides for g_comp_stride < B, viol_step_stride < B with
+ * T > 1, and g_seq rows that are neither step-major nor component-major (pcg_rollout_strided's rule for the observation
+ * rows with ncon in place of Nobs).
+ * Reads the plan and the policies and writes neither; no allocation, no memset: safe under stream capture.
+ * Not here: constraint expressions and user models, float32 networks, per-env parameters, adaptive integrators; the
+ * open-loop pcg_rollout / pcg_rollout_strided still keep only the last step's rows. */
+PCG_API int pcg_rollout_policy_cons(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* policy, int32_t t0, int32_t T,
+                                    double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                                    int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                    int64_t rew_step_stride, int32_t record_next_action, double* g_seq,
+                                    int64_t g_step_stride, int64_t g_comp_stride, uint8_t* viol_seq,
+                                    int64_t viol_step_stride, uint64_t seed, void* stream);
+PCG_API int pcg_rollout_actor_cons(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* actor, const pcg_policy* critic,
+                                   const double* sigma, int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride,
+                                   int64_t a_comp_stride, double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride,
+                                   double* logp_out, int64_t logp_step_stride, double* value_out,
+                                   int64_t value_step_stride, double* obs_seq, int64_t obs_step_stride,
+                                   int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                                   int32_t record_next_action, double* g_seq, int64_t g_step_stride, int64_t g_comp_stride,
+                                   uint8_t* viol_seq, int64_t viol_step_stride, uint64_t seed, void* stream);
 /* Host only: c0 = -(sum_i log sigma_i + na/2 log 2 pi), summed in ascending order in fp64 -- the constant
  * pcg_rollout_actor passes to its kernel.  NaN for a NULL / non-positive / non-finite sigma or na outside 1..PCG_MAX_NA. */
 PCG_API double pcg_actor_logp_const(const double* sigma, int32_t na);

@@ -211,6 +211,8 @@ EXPORTS = [
     "pcg_rollout_policy",
     "pcg_plan_prepare_closed_loop",
     "pcg_rollout_actor",
+    "pcg_rollout_policy_cons",
+    "pcg_rollout_actor_cons",
     "pcg_actor_logp_const",
     "pcg_policy_noise",
     "pcg_step_autoreset",
@@ -285,6 +287,13 @@ def declare(lib):
     lib.pcg_rollout_actor.argtypes = [vp, C.POINTER(pcg_buffers), vp, vp, _pd, C.c_int32, C.c_int32,
                                       vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                       vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, C.c_uint64, vp]
+    # (the two on plans with constraint rows: the same lists with g_seq / strides / viol_seq / stride ahead of the seed)
+    lib.pcg_rollout_policy_cons.restype = C.c_int
+    lib.pcg_rollout_policy_cons.argtypes = (lib.pcg_rollout_policy.argtypes[:-2] + [vp, C.c_int64, C.c_int64, vp, C.c_int64]
+                                            + lib.pcg_rollout_policy.argtypes[-2:])
+    lib.pcg_rollout_actor_cons.restype = C.c_int
+    lib.pcg_rollout_actor_cons.argtypes = (lib.pcg_rollout_actor.argtypes[:-2] + [vp, C.c_int64, C.c_int64, vp, C.c_int64]
+                                           + lib.pcg_rollout_actor.argtypes[-2:])
     lib.pcg_actor_logp_const.restype = C.c_double
     lib.pcg_actor_logp_const.argtypes = [_pd, C.c_int32]
     lib.pcg_policy_noise.restype = C.c_int

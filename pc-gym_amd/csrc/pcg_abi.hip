@@ -22,6 +22,7 @@
 #include <set>
 #include <sstream>
 #include <string>
+#include <type_traits>
 
 namespace pcg {
 
@@ -1401,29 +1402,36 @@ static bool step_lean(StepCall& s, int* rc) {
 // Feature-masked pipelined kernel (pcg_step_feat.hpp): RK4 plans of the small models with anything beyond the
 // lean step switched on.  Needs two envs per lane (even B, 16-byte rows); the smallest instantiation whose mask
 // covers what this launch uses is taken.  PCG_OPT_VARIANT 1 forces the classic one-env-per-lane kernel (A/B).
-static bool step_feat(StepCall& s, int* rc) {
-  const pcg_plan* p = s.p; const Kernels& k = s.k; const pcg_buffers* io = s.io;
+// (the choice on its own: the index into k.feat, or -1 -- also asked by the constrained closed-loop rollouts, whose rows are
+// summed in the order of the kernel pcg_step would run on the same buffers: feat_route_of_step)
+static int feat_pick(const pcg_plan* p, const Kernels& k, const pcg_buffers* io, int pe, bool lds_st, bool auto_reset) {
   const DevConst& c = p->hc;
-  if (p->integrator_id != PCG_INT_RK4 || k.nfeat == 0 || s.lds_st || !(p->variant == 0 || p->variant == 4 || p->variant == 5))
-    return false;
+  if (p->integrator_id != PCG_INT_RK4 || k.nfeat == 0 || lds_st || !(p->variant == 0 || p->variant == 4 || p->variant == 5))
+    return -1;
   // observation noise, per-env step counters, per-env / Gaussian disturbances: the classic kernel is the faster one
   // (measured), and a lock-stepped same-launch reset needs every env to end together
-  if (s.pe || io->d || (c.flags & PCG_F_NOISE) || ((c.flags & PCG_F_GAUSS_DIST) && c.nd > 0) ||
-      (s.auto_reset && (c.flags & PCG_F_DONE_ON_CONS) && c.ncon > 0) || (io->B % 2 != 0) || !al16(io->x) || !al16(io->a) ||
+  if (pe || io->d || (c.flags & PCG_F_NOISE) || ((c.flags & PCG_F_GAUSS_DIST) && c.nd > 0) ||
+      (auto_reset && (c.flags & PCG_F_DONE_ON_CONS) && c.ncon > 0) || (io->B % 2 != 0) || !al16(io->x) || !al16(io->a) ||
       !al16(io->obs) || !al16(io->rew) || !al2(io->done) || !al2(io->viol) || !al2(io->status) || !al16(io->a_save) ||
       !al16(io->u_prev) || !al16(io->g) || !al16(io->g_pre))
-    return false;
+    return -1;
   unsigned need = 0;
   if (c.ncon > 0) need |= FT_CONS;
   if (c.flags & PCG_F_A_DELTA) need |= FT_ADELTA;
   if (c.flags & PCG_F_REWARD_TRACK) need |= FT_TRACK;
   if (c.flags & PCG_F_REWARD_BATCH) need |= FT_BATCH;
-  if (s.auto_reset) need |= FT_AR;
+  if (auto_reset) need |= FT_AR;
   int best = -1;
   for (int i = 0; i < k.nfeat; ++i)
     if ((k.feat[i].mask & need) == need &&
         (best < 0 || __builtin_popcount(k.feat[i].mask) < __builtin_popcount(k.feat[best].mask)))
       best = i;
+  return best;
+}
+
+static bool step_feat(StepCall& s, int* rc) {
+  const pcg_plan* p = s.p; const Kernels& k = s.k; const pcg_buffers* io = s.io;
+  const int best = feat_pick(p, k, io, s.pe, s.lds_st, s.auto_reset);
   if (best < 0) return false;
   int bpc = p->feat_occ[best];
   if (p->stream_bpc > 0 && p->stream_bpc < bpc) bpc = p->stream_bpc;
@@ -1816,6 +1824,12 @@ struct SeqRec {  // a sequence the head records, with its component stride; null
   const double* seq;
   int64_t comp_stride;
 };
+struct ConsRec {  // what the constrained entry points record beside: rows [T][ncon][B]-like, flags [T][B]-like
+  double* g_seq;
+  int64_t g_ss, g_cs;
+  uint8_t* viol_seq;
+  int64_t v_ss;
+};
 
 // whether a closed-loop kernel exists for this run-time compiled plan: the plans the built-in path takes
 static bool jit_closed_loop_ok(const pcg_plan* p) {
@@ -1845,9 +1859,12 @@ static int jit_prepare_closed_loop(pcg_plan* p) {
 static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return p->jit_pol; }
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
 
+// `cons`: the entry points for plans WITH constraint rows (pcg_rollout_policy_cons / _actor_cons: table_f32 is null) -- the
+// same checks with the plan's side turned round: rows are required, and what their kernels are not built for (a plan with
+// run-time compiled code, a float32 network) is refused here, before the sizes
 template <class Fn>
 static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2],
-                            Fn (Kernels::*table_f32)[2], StepArgs* a, Fn* fn) {
+                            Fn (Kernels::*table_f32)[2], StepArgs* a, Fn* fn, bool cons = false) {
   PCG_TRY(fill_args(p, io, a));
   if (!q) return PCG_E_NULL;
   if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
@@ -1855,6 +1872,13 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, and every integrator
   // but the two fixed-step schemes
   const int ls = lean_scheme(p->integrator_id);
+  if (cons) {
+    if (c.ncon <= 0 || p->jit_fn[0] || io->t || c.nunc > 0 || ls < 0 || q->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;
+    *fn = (kernels(p->kid).*table)[ls];
+    if (!*fn) return PCG_E_UNSUPPORTED;
+    if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+    return PCG_OK;
+  }
   if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
   // (a run-time compiled plan has no ahead-of-time kernel: closed_loop_launch takes its own module's)
   *fn = p->jit_fn[0] ? nullptr : (kernels(p->kid).*(q->dtype == PCG_POL_F32 ? table_f32 : table))[ls];
@@ -1863,9 +1887,20 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   return PCG_OK;
 }
 
+// whether pcg_step on these buffers would take the feature-masked kernel (step_impl's routes, for a lock-stepped built-in
+// plan with rows and without per-env parameters: io->a is the caller's per-step action row, io->d is not given in a closed loop)
+static bool feat_route_of_step(const pcg_plan* p, const pcg_buffers* io) {
+  const Kernels& k = kernels(p->kid);
+  pcg_buffers b = *io;
+  b.a = nullptr; b.d = nullptr;
+  return feat_pick(p, k, &b, 0, lds_stages_on(p, k), false) >= 0;
+}
+
+// `cons` (the constrained entry points): the recorded rows and flags; the launch then carries a ConsArgs as its third argument
 template <class Fn, class HeadArgs>
 static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, Fn fn, const HeadArgs& head, const ClosedLoopRun& r,
-                              std::initializer_list<SeqRec> head_recs, int f32, int late_status, void* stream) {
+                              std::initializer_list<SeqRec> head_recs, int f32, int late_status, void* stream,
+                              const ConsRec* cons = nullptr) {
   const DevConst& c = p->hc;
   if (r.T < 1 || r.t0 < 0 || (int64_t)r.t0 + (int64_t)r.T > 0x7fffffffLL) return PCG_E_VALUE;
   if (io->B == 0) return PCG_OK;
@@ -1875,6 +1910,18 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
   if (r.obs_seq && r.obs_cs < io->B) return PCG_E_DIM;
   for (const SeqRec& h : head_recs)
     if (h.seq && h.comp_stride < io->B) return PCG_E_DIM;
+  if (cons) {
+    // the rows a rollout WRITES must not overlap: flag rows a full batch apart, constraint rows either step-major or
+    // component-major (the reference's axis order) -- pcg_rollout_strided's rule for the observation rows
+    const int64_t B = io->B, n = c.ncon;
+    if (cons->g_seq && cons->g_cs < B) return PCG_E_DIM;
+    if (cons->viol_seq && r.T > 1 && cons->v_ss < B) return PCG_E_DIM;
+    if (cons->g_seq) {
+      const bool step_major = r.T == 1 || cons->g_ss >= (n - 1) * cons->g_cs + B;
+      const bool comp_major = cons->g_ss >= B && (n == 1 || cons->g_cs >= (int64_t)(r.T - 1) * cons->g_ss + B);
+      if (!step_major && !comp_major) return PCG_E_DIM;
+    }
+  }
   // what the float32 form adds, after every other check: networks of two dtypes in one call (late_status), and a plan with
   // run-time compiled code, whose closed-loop module carries the fp64 kernels alone -- nothing compiled, nothing launched
   if (late_status != PCG_OK) return late_status;
@@ -1898,7 +1945,18 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
     return (int)hipModuleLaunchKernel(cov_jit(jit_head_fn(p, head)), grid_for(io->B), 1, 1, BLOCK, 1, 1, 0, (hipStream_t)stream,
                                       argv, nullptr);
   }
-  hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head);
+  if constexpr (std::is_invocable_v<Fn, const StepArgs, const HeadArgs, const ConsArgs>) {
+    ConsArgs g;
+    g.g_seq = cons->g_seq; g.g_ss = cons->g_ss; g.g_cs = cons->g_cs;
+    g.viol_seq = cons->viol_seq; g.v_ss = cons->v_ss;
+    // (env_pre's own pre-step check and store_out see no row storage: the kernel writes the rows it summed itself)
+    g.g_last = a.g; g.g_pre = a.g_pre;
+    a.g = nullptr; a.g_pre = nullptr;
+    g.order_w = feat_route_of_step(p, io) ? 1 : 0;
+    hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head, g);
+  } else {
+    hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head);
+  }
   return (int)hipGetLastError();
 }
 }  // extern "C++"
@@ -1916,6 +1974,23 @@ int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, 
   pa.record_next = record_next_action ? 1 : 0;
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, q->dtype == PCG_POL_F32, PCG_OK, stream);
+}
+
+int pcg_rollout_policy_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
+                            int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
+                            int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
+                            double* g_seq, int64_t g_step_stride, int64_t g_comp_stride, uint8_t* viol_seq,
+                            int64_t viol_step_stride, uint64_t seed, void* stream) {
+  StepArgs a;
+  PolConsFn fn;
+  PCG_TRY(closed_loop_open<PolConsFn>(p, io, q, &Kernels::roll_policy_cons, nullptr, &a, &fn, true));
+  PolicyArgs pa;
+  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
+  pa.record_next = record_next_action ? 1 : 0;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
+  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, 0, PCG_OK, stream, &rec);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {
@@ -1975,6 +2050,43 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
   const int mixed = (v && v->dtype != q->dtype) ? PCG_E_UNSUPPORTED : PCG_OK;
   return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, q->dtype == PCG_POL_F32,
                             mixed, stream);
+}
+
+int pcg_rollout_actor_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, const pcg_policy* v, const double* sigma,
+                           int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                           double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride, double* logp_out,
+                           int64_t logp_step_stride, double* value_out, int64_t value_step_stride, double* obs_seq,
+                           int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                           int32_t record_next_action, double* g_seq, int64_t g_step_stride, int64_t g_comp_stride,
+                           uint8_t* viol_seq, int64_t viol_step_stride, uint64_t seed, void* stream) {
+  StepArgs a;
+  ActConsFn fn;
+  PCG_TRY(closed_loop_open<ActConsFn>(p, io, q, &Kernels::roll_actor_cons, nullptr, &a, &fn, true));
+  const DevConst& c = p->hc;
+  if (v) {
+    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
+    if (v->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;  // (the constrained kernels are built for fp64 networks)
+    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
+    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
+  }
+  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
+  if (!sigma) return PCG_E_NULL;
+  for (int i = 0; i < c.na; ++i)
+    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  ActorArgs aa;
+  std::memset(&aa, 0, sizeof(aa));
+  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
+  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
+  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
+  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
+  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
+  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
+  aa.c0 = pcg_actor_logp_const(sigma, c.na);
+  aa.record_next = record_next_action ? 1 : 0;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
+  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, 0, PCG_OK, stream, &rec);
 }
 
 int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {

@@ -1154,12 +1154,18 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #ifndef __HIPCC_RTC__
 // (ahead-of-time only: a plan's run-time compiled closed-loop module carries the fp64 kernels alone)
 #include "pcg_rollout_policy_f32.hpp"
+// (... nor the kernels of the plans with constraint rows: such a plan with run-time compiled code steps)
+#include "pcg_rollout_cons.hpp"
 #endif
 namespace pcg {
 
 using StepFn = void (*)(const StepArgs);
 using PolFn = void (*)(const StepArgs, const PolicyArgs);
 using ActFn = void (*)(const StepArgs, const ActorArgs);
+#ifndef __HIPCC_RTC__
+using PolConsFn = void (*)(const StepArgs, const PolicyArgs, const ConsArgs);
+using ActConsFn = void (*)(const StepArgs, const ActorArgs, const ConsArgs);
+#endif
 
 #ifndef __HIPCC_RTC__
 // ---------------------------------------------------------------------------
@@ -1213,6 +1219,8 @@ struct Kernels {
   ActFn roll_actor[2];               // ... with a Gaussian actor (sampled action, log-prob) and an optional critic
   PolFn roll_policy_f32[2];          // the same two with the networks evaluated in float32 (pcg_rollout_policy_f32.hpp)
   ActFn roll_actor_f32[2];
+  PolConsFn roll_policy_cons[2];     // the fp64 two on plans with constraint rows, recording the rows (pcg_rollout_cons.hpp)
+  ActConsFn roll_actor_cons[2];
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1281,6 +1289,10 @@ Kernels make_kernels() {
   k.roll_policy_f32[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel_f32<M, PCG_INT_CV8>;
   k.roll_actor_f32[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel_f32<M, PCG_INT_RK4>;
   k.roll_actor_f32[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel_f32<M, PCG_INT_CV8>;
+  k.roll_policy_cons[lean_scheme(PCG_INT_RK4)] = rollout_cons_policy_kernel<M, PCG_INT_RK4>;
+  k.roll_policy_cons[lean_scheme(PCG_INT_CV8)] = rollout_cons_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_actor_cons[lean_scheme(PCG_INT_RK4)] = rollout_cons_actor_kernel<M, PCG_INT_RK4>;
+  k.roll_actor_cons[lean_scheme(PCG_INT_CV8)] = rollout_cons_actor_kernel<M, PCG_INT_CV8>;
   // Tsit5 (the reference's jax method): general kernel, both counter modes, and the integration hook
   k.step[PCG_INT_TSIT5][0][0][0] = k.step[PCG_INT_TSIT5][0][0][1] = step_kernel<M, PCG_INT_TSIT5, false, false, true>;
   k.step[PCG_INT_TSIT5][1][0][0] = k.step[PCG_INT_TSIT5][1][0][1] = step_kernel<M, PCG_INT_TSIT5, true, false, true>;

@@ -379,6 +379,66 @@ class VecEnv:
         self.t += T
         return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
 
+    def _cons_buffers(self, T, collect_g, collect_viol):
+        """(g (T, ncon, B) | None, viol (T, B) uint8 | None) of a fused closed-loop rollout on a plan with constraint rows"""
+        torch = _torch()
+        if not self.spec.ncon:
+            raise ValueError("this plan has no constraint rows: use rollout_policy() / rollout_actor()")
+        g, = self._seq_buffers(((T, self.spec.ncon, self.B), collect_g))
+        viol = torch.empty((T, self.B), dtype=torch.uint8, device=self.device) if collect_viol else None
+        return g, viol
+
+    def rollout_policy_cons(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
+                            record_next_action=False, collect_g=True, collect_viol=True):
+        """``rollout_policy`` on a plan WITH constraint rows (``pcg_rollout_policy_cons``): the same launch, which also records
+        every step's rows and violation flag.  Returns a dict: "a" (T [+1], na, B), "obs" (T, Nobs, B), "rew" (T, B),
+        "g" (T, ncon, B), "viol" (T, B) bool (a view of the kernel's bytes); None where not asked for.  ``env.g`` /
+        ``env.viol`` / ``env.done`` hold the last step afterwards, ``env.g_pre`` the pre-step check of a call that starts at
+        t = 0 -- what the step() loop leaves, bit for bit.  An env whose ``done`` is set mid-episode (``done_on_cons_vio``) keeps
+        stepping, as in that loop.  Plans the kernel does not take (no rows, constraint expressions, user models, per-env
+        parameters, integrators other than rk4 / cv8) and float32 policies raise PcgError."""
+        if self.per_env_t:
+            raise ValueError("rollout_policy_cons() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        g_seq, viol = self._cons_buffers(T, collect_g, collect_viol)
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_policy_cons(
+            self._plan, self._bufp, policy.handle(dev), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), _ptr(g_seq), s.ncon * B, B, _ptr(viol), B,
+            self._episode_seed(), self._stream()), "pcg_rollout_policy_cons")
+        self.t += T
+        return {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "g": g_seq,
+                "viol": viol.view(_torch().bool) if viol is not None else None}
+
+    def rollout_actor_cons(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
+                           collect_logp=True, collect_values=True, record_next_action=False, collect_g=True,
+                           collect_viol=True):
+        """``rollout_actor`` on a plan WITH constraint rows (``pcg_rollout_actor_cons``): its dict plus "g" (T, ncon, B) and
+        "viol" (T, B) bool, as ``rollout_policy_cons`` records them; float64 networks only."""
+        if self.per_env_t:
+            raise ValueError("rollout_actor_cons() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
+            ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        g_seq, viol = self._cons_buffers(T, collect_g, collect_viol)
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_actor_cons(
+            self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
+            ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
+            _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), _ptr(g_seq), s.ncon * B, B, _ptr(viol), B,
+            self._episode_seed(), self._stream()), "pcg_rollout_actor_cons")
+        self.t += T
+        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq, "g": g_seq,
+                "viol": viol.view(_torch().bool) if viol is not None else None}
+
     def policy_noise(self, t=None, out=None):
         """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the
         current episode -- same Philox keys, same bits -- for a caller that samples outside the kernel."""

@@ -232,6 +232,15 @@ def fused_policy_ok(spec, policy):
             and not (policy.dtype == "float32" and _runtime_compiled(spec)))
 
 
+def fused_cons_ok(spec, policy):
+    """the plans pcg_rollout_policy_cons takes (include/pcgym_hip.h): those of pcg_rollout_policy WITH affine constraint rows,
+    recorded per step -- fixed-step RK4 / CV8, no per-env parameters, built-in plans only (a user model, a reward or constraint
+    expression runs from a module that carries the unconstrained kernels alone), a float64 policy of the plan's sizes"""
+    return (isinstance(policy, MLPPolicy) and spec.integrator in ("rk4", "cv8") and bool(spec.ncon) and not spec.nunc
+            and not _runtime_compiled(spec) and policy.dtype != "float32"
+            and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
+
+
 def _runtime_compiled(spec):
     """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
     return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)
@@ -370,3 +379,10 @@ def fused_actor_ok(spec, ac):
     (if any) of the plan's observation size that the device form can hold"""
     return (isinstance(ac, GaussianActorCritic) and fused_policy_ok(spec, ac.actor) and ac.actor.out_map != "tanh"
             and (ac.critic is None or (ac.critic.n_in == spec.nobs and ac.critic.validate() == 0)))
+
+
+def fused_actor_cons_ok(spec, ac):
+    """the plans and networks pcg_rollout_actor_cons takes: those of pcg_rollout_policy_cons for the actor, no tanh map, and a
+    float64 critic (if any) of the plan's observation size that the device form can hold"""
+    return (isinstance(ac, GaussianActorCritic) and fused_cons_ok(spec, ac.actor) and ac.actor.out_map != "tanh"
+            and (ac.critic is None or (ac.critic.n_in == spec.nobs and ac.critic.dtype != "float32" and ac.critic.validate() == 0)))

@@ -15,7 +15,8 @@ every array on the GPU in the reference's axis order:
 ``reps`` of the reference (independent repetitions of one env) is the env axis B here.
 Closed loop: ``policy(obs (B, Nobs) tensor) -> (B, na)`` (or ``(na, B)``) tensor, one
 kernel launch per step -- or, for a declarative :class:`~pcgym_amd.policy.MLPPolicy` on a plan that qualifies, ONE launch
-for the whole episode with the policy evaluated in the kernel (``pcg_rollout_policy``).  Open loop (``actions`` given, no constraint rows to record): the fused
+for the whole episode with the policy evaluated in the kernel (``pcg_rollout_policy``; ``pcg_rollout_policy_cons`` on a plan
+with constraint rows, which records the rows of every step).  Open loop (``actions`` given, no constraint rows to record): the fused
 ``pcg_rollout_strided`` kernel writes straight into these layouts, state in registers.
 """
 from __future__ import annotations
@@ -26,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .policy import fused_actor_ok, fused_policy_ok
+from .policy import fused_actor_cons_ok, fused_actor_ok, fused_cons_ok, fused_policy_ok
 
 
 def _torch():
@@ -75,7 +76,9 @@ def collect_rollouts(env, policy=None, actions=None):
 
     policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop); an ``MLPPolicy`` is evaluated inside
               the fused rollout kernel when the plan qualifies (``fused_policy_ok``: RK4 / CV8, no constraint rows, no
-              per-env parameters; user models and reward expressions included) and like any other callable otherwise, or
+              per-env parameters; user models and reward expressions included -- or ``fused_cons_ok``: a built-in plan
+              WITH affine constraint rows, whose rows the kernel of ``pcg_rollout_policy_cons`` records into ``g``) and
+              like any other callable otherwise, or
     actions : (N, na, B) tensor of policy outputs (open loop; row N-1 is only recorded in ``u``).
 
     Recording is zero-copy: each step's kernel writes its observation / reward rows straight into the trajectory
@@ -136,6 +139,21 @@ def collect_rollouts(env, policy=None, actions=None):
         _lib.check(rc, "pcg_rollout_policy")
         env.t += N - 1
         return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
+    if policy is not None and fused_cons_ok(s, policy):
+        # the same on a plan with constraint rows (pcg_rollout_policy_cons): the kernel also writes every step's rows into
+        # g[:, 1:] in the reference's axis order; g[:, 0] is the pre-step check of the first step (pcgym.py:414-420)
+        x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
+        u = torch.empty((s.na, N, B), dtype=f64, device=dev)
+        x[:, 0] = env.obs_soa
+        env._buf.d = None
+        rc = env._lib.pcg_rollout_policy_cons(
+            env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
+            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, g[:, 1:].data_ptr(), B, N * B, None, 0,
+            env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_policy_cons")
+        env.t += N - 1
+        g[:, 0, 0] = env.g_pre
+        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0), "g": g}
     # per-step path: step-major storage, the env's kernels write into it
     xs = torch.empty((N, s.nobs, B), dtype=f64, device=dev)
     us = torch.empty((N, s.na, B), dtype=f64, device=dev)
@@ -184,7 +202,7 @@ def gae(rew, val, gamma=0.99, lam=0.95, bootstrap_last=False):
     return adv, adv + val[:T]
 
 
-def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None):
+def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None, record_cons=False):
     """One episode (N - 1 steps) of all B envs under the stochastic actor-critic ``ac`` (a
     :class:`~pcgym_amd.policy.GaussianActorCritic` with a critic): what an on-policy trainer such as PPO collects.
 
@@ -198,7 +216,16 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
 
     Route: ONE launch (``pcg_rollout_actor``) when the plan and the networks qualify (``fused_actor_ok``: RK4 / CV8, no
     constraint rows, no per-env parameters, no tanh map; user models and reward expressions included); otherwise -- or with ``fused=False`` -- one
-    ``env.step`` per step with the sample formed in torch from ``env.policy_noise``, i.e. from the same random bits."""
+    ``env.step`` per step with the sample formed in torch from ``env.policy_noise``, i.e. from the same random bits.
+
+    ``record_cons=True`` (plans with constraint rows only, ValueError otherwise) adds what a constrained trainer needs -- a
+    cost signal, a Lagrangian term, a mask after ``done_on_cons_vio``:
+        g     (N-1, ncon, B)  the constraint rows after every step
+        g_pre (ncon, B)       the rows of the pre-step check of the first step (pcgym.py:414-420)
+        viol  (N-1, B)        bool, any row > 0
+    on both routes: ONE launch (``pcg_rollout_actor_cons``) when ``fused_actor_cons_ok`` (a built-in RK4 / CV8 plan with
+    affine rows, float64 networks), the per-step loop otherwise or with ``fused=False``; ``fused=True`` then raises only
+    when ``fused_actor_cons_ok`` is false.  An env whose ``done`` is set mid-episode keeps stepping on both routes."""
     torch = _torch()
     s = env.spec
     B, N, dev, f64 = env.B, s.N, env.device, torch.float64
@@ -216,10 +243,28 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
     rew = torch.empty((T, B), dtype=f64, device=dev)
     o, _ = env.reset()
     obs[0] = env.obs_soa
-    ok = fused_actor_ok(s, ac)
+    if record_cons and not s.ncon:
+        raise ValueError("record_cons: this plan has no constraint rows")
+    ok = fused_actor_cons_ok(s, ac) if record_cons else fused_actor_ok(s, ac)
     if fused and not ok:
         raise ValueError("this plan / actor-critic does not qualify for the fused call")
-    if ok and fused is not False:
+    cons = {}
+    if record_cons:
+        cons = {"g": torch.empty((T, s.ncon, B), dtype=f64, device=dev), "g_pre": None,
+                "viol": torch.empty((T, B), dtype=torch.uint8, device=dev)}
+    if record_cons and ok and fused is not False:
+        u = torch.empty((N, s.na, B), dtype=f64, device=dev)
+        env._buf.d = None
+        rc = env._lib.pcg_rollout_actor_cons(
+            env._plan, env._bufp, ac.actor.handle(dev), ac.critic.handle(dev), ac.sigma.ctypes.data_as(C.POINTER(C.c_double)),
+            0, T, None, 0, 0, u.data_ptr(), s.na * B, B, logp.data_ptr(), B, val.data_ptr(), B,
+            obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, cons["g"].data_ptr(), s.ncon * B, B,
+            cons["viol"].data_ptr(), B, env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_actor_cons")
+        env.t += T
+        act = u[:T]
+        cons["g_pre"] = env.g_pre.clone()
+    elif ok and fused is not False:
         # (row N-1 of the samples is drawn and dropped: only its value, the bootstrap value, is kept)
         u = torch.empty((N, s.na, B), dtype=f64, device=dev)
         env._buf.d = None
@@ -242,9 +287,18 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
                 val[i] = ac.value(o)
                 env.bind_outputs(obs[i + 1], rew[i])
                 o, _, _, _, _ = env.step(ac.action(u))
+                if record_cons:
+                    if i == 0:
+                        cons["g_pre"] = env.g_pre.clone()
+                    cons["g"][i] = env.g
+                    cons["viol"][i] = env.viol
             val[T] = ac.value(o)
     adv, ret = gae(rew, val, gamma, lam, bootstrap_last)
-    return {"obs": obs, "act": act, "logp": logp[:T], "val": val, "rew": rew, "adv": adv, "ret": ret}
+    out = {"obs": obs, "act": act, "logp": logp[:T], "val": val, "rew": rew, "adv": adv, "ret": ret}
+    if record_cons:
+        cons["viol"] = cons["viol"].view(torch.bool)
+        out.update(cons)
+    return out
 
 
 class reproducibility_metric:

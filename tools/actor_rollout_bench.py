@@ -13,6 +13,10 @@ compared is the median:
     c   collect_rollouts(env, policy=ac.actor)   the deterministic fused call, same actor
     a0  reset + VecEnv.rollout_actor without a critic (samples, log-probabilities, observations, rewards recorded)
 The condition: a is not slower than b for any shape (collect_onpolicy takes the fused call wherever the plan qualifies).
+With --constraints the workload is the constraint showcase (scenario cstr_cons_pen_norm under integrator="rk4") and three routes
+alternate: ac = collect_onpolicy(env, ac, record_cons=True), fused (pcg_rollout_actor_cons: rows and flags of every step
+recorded); bc = the same with fused=False, its per-step route; au = collect_onpolicy fused on the unconstrained cstr_canonical
+under rk4, the reference for what the 8 * ncon + 1 recorded bytes per env step cost.
 With --dtype float32 three routes alternate instead: a32 = collect_onpolicy fused with float32 networks, a64 = the same with
 float64 networks of the same (rounded) weights, b32 = the per-step route of the float32 networks.
 """
@@ -81,14 +85,65 @@ def f32_rows(a, p, VecEnv, collect_onpolicy, torch):
     return lines
 
 
+def cons_rows(a, VecEnv, collect_onpolicy, torch):
+    import copy
+
+    import scenarios as SC
+
+    p = dict(copy.deepcopy(SC.scenarios()["cstr_cons_pen_norm"]["env_params"]), integrator="rk4")
+    p_ref = dict(copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"]), integrator="rk4")
+    lines = ["# --constraints: cstr_cons_pen_norm, integrator rk4: ac = collect_onpolicy(record_cons=True) fused (pcg_rollout_actor_cons), "
+             "bc = its per-step route, au = collect_onpolicy fused on the unconstrained cstr_canonical, rk4"]
+    for name in a.shapes.split(","):
+        envs = {"ac": VecEnv(dict(p), n_envs=a.B, seed=1), "bc": VecEnv(dict(p), n_envs=a.B, seed=1), "au": VecEnv(dict(p_ref), n_envs=a.B, seed=1)}
+        spec = envs["ac"].spec
+        assert spec.ncon and (envs["au"].spec.nobs, envs["au"].spec.na, envs["au"].spec.N) == (spec.nobs, spec.na, spec.N)
+        ac = make_ac(spec, SHAPES[name])
+        steps = spec.N - 1
+        routes = {"ac": lambda: collect_onpolicy(envs["ac"], ac, record_cons=True),
+                  "bc": lambda: collect_onpolicy(envs["bc"], ac, record_cons=True, fused=False), "au": lambda: collect_onpolicy(envs["au"], ac)}
+        times = {k: [] for k in routes}
+        viol = float("nan")
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                if rep == 0 and k == "ac":
+                    viol = float(d["viol"].double().mean())
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        extra = (8 * spec.ncon + 1) * a.B * steps
+        verdict = "fused not slower than per-step" if med["ac"] <= med["bc"] else "FUSED SLOWER THAN PER-STEP"
+        lines.append(f"{name:7s} ac {us['ac']:8.2f}  bc {us['bc']:8.2f}  au {us['au']:8.2f} us/step   bc / ac = {med['bc'] / med['ac']:.2f}   "
+                     f"ac / au = {med['ac'] / med['au']:.3f}   ac - au = {med['ac'] - med['au']:.3f} ms per episode for {extra / 1e6:.1f} MB of rows and "
+                     f"flags (ncon = {spec.ncon})   {a.B * steps / med['ac'] / 1e-3:.3e} env-steps/s fused   entries violated {viol:.3f}   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        ac.close()
+        del envs
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
+    ap.add_argument("--constraints", action="store_true", help="the constraint showcase: fused-cons against per-step (and the unconstrained fused call)")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.constraints and a.dtype != "float64":
+        ap.error("--constraints: the constrained kernels take float64 networks")
     import torch
 
     import bench
@@ -104,7 +159,9 @@ def main():
     p = bench.workload_params()
     if a.dtype == "float32":
         lines += f32_rows(a, p, VecEnv, collect_onpolicy, torch)
-    for name in ([] if a.dtype == "float32" else a.shapes.split(",")):
+    if a.constraints:
+        lines = lines[:1] + cons_rows(a, VecEnv, collect_onpolicy, torch)
+    for name in ([] if a.dtype == "float32" or a.constraints else a.shapes.split(",")):
         envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("a", "b", "c", "a0")}
         spec = envs["a"].spec
         ac, ac0 = make_ac(spec, SHAPES[name]), make_ac(spec, SHAPES[name], critic=False)

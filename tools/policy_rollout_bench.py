@@ -9,6 +9,10 @@ Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s
 both produce the reference's x (Nx, N, B) / u (na, N, B) / r (1, N, B) arrays.  The two routes alternate inside one
 process (`reps` pairs after one warm-up pair each); times are device-event times of whole episodes, the figure compared is
 the median.  The 2 x 64 policy is also reported as a share of the fp64 vector peak (FMAs of the policy alone).
+With --constraints the workload is the constraint showcase (scenario cstr_cons_pen_norm under integrator="rk4": two affine rows,
+r_penalty): the fused call is pcg_rollout_policy_cons, which also records the rows of every step into g; the per-step route
+records them from env.g; a third route, the unconstrained fused call on cstr_canonical under rk4, alternates with them as the
+reference for what the rows cost (8 * ncon recorded bytes per env step; the collector does not ask for the flags).
 With --dtype float32 three routes alternate: the float32 fused call (rollout_policy_kernel_f32), the float64 fused call on the
 same (float32-rounded) weights, and the per-step route with the float32 callable.
 """
@@ -103,8 +107,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
+    ap.add_argument("--constraints", action="store_true", help="the constraint showcase: fused-cons against per-step (and the unconstrained fused call)")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.constraints and a.dtype != "float64":
+        ap.error("--constraints: the constrained kernels take float64 policies")
     import torch
 
     import bench
@@ -116,6 +123,16 @@ def main():
              f"({os.path.relpath(_lib.LIB_PATH, ROOT)})  {torch.cuda.get_device_name(0)}",
              "# cstr, RK4 x 1, N = 60: one episode = 59 closed-loop steps; ms per episode, median of the interleaved repeats"]
     p = bench.workload_params()
+    p_ref = None
+    if a.constraints:
+        import copy
+
+        import scenarios as SC
+
+        p = dict(copy.deepcopy(SC.scenarios()["cstr_cons_pen_norm"]["env_params"]), integrator="rk4")
+        p_ref = dict(copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"]), integrator="rk4")
+        lines[1] = ("# --constraints: cstr_cons_pen_norm, integrator rk4 (fused = pcg_rollout_policy_cons, rows recorded); uncon = the "
+                    "unconstrained fused call on cstr_canonical, rk4; ms per episode, median of the interleaved repeats")
     if a.dtype == "float32":
         lines += f32_rows(a, p, VecEnv, collect_rollouts, torch)
     for name in ([] if a.dtype == "float32" else a.shapes.split(",")):
@@ -124,6 +141,11 @@ def main():
         pol = make_policy(spec, SHAPES[name])
         steps = spec.N - 1
         routes = {"fused": lambda: collect_rollouts(e_f, policy=pol), "per_step": lambda: collect_rollouts(e_s, policy=lambda o: pol(o))}
+        e_u = None
+        if p_ref is not None:
+            e_u = VecEnv(dict(p_ref), n_envs=a.B, seed=1)
+            assert spec.ncon and (e_u.spec.nobs, e_u.spec.na, e_u.spec.N) == (spec.nobs, spec.na, spec.N)
+            routes["uncon"] = lambda: collect_rollouts(e_u, policy=pol)
         times = {k: [] for k in routes}
         for rep in range(a.reps + 1):  # (pair 0 warms both routes up)
             for k, fn in routes.items():
@@ -147,6 +169,12 @@ def main():
                      f"per-step / fused = {med['per_step'] / med['fused']:.2f}   policy FMAs per env step {fm}, "
                      f"= {100 * share:.1f} % of the fp64 vector peak in the fused call   actions inside the box {inside:.2f}")
         lines.append(f"        fused repeats {[round(t, 3) for t in times['fused']]}  per-step repeats {[round(t, 3) for t in times['per_step']]}")
+        if e_u is not None:
+            extra = 8 * spec.ncon * a.B * steps  # bytes of recorded rows per episode
+            lines.append(f"        uncon {med['uncon']:9.3f} ms ({us['uncon']:8.2f} us/step)   fused-cons / uncon = {med['fused'] / med['uncon']:.3f}   "
+                         f"fused-cons - uncon = {med['fused'] - med['uncon']:.3f} ms for {extra / 1e6:.1f} MB of rows "
+                         f"(ncon = {spec.ncon})   uncon repeats {[round(t, 3) for t in times['uncon']]}")
+            e_u.close()
         e_f.close(), e_s.close(), pol.close()
         del e_f, e_s
         torch.cuda.empty_cache()
