@@ -642,6 +642,37 @@ PCG_API int pcg_rollout_actor_cons(pcg_plan* plan, const pcg_buffers* io, const 
                                    int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
                                    int32_t record_next_action, double* g_seq, int64_t g_step_stride, int64_t g_comp_stride,
                                    uint8_t* viol_seq, int64_t viol_step_stride, uint64_t seed, void* stream);
+/* The two closed-loop calls on plans WITH per-env parameters (additive under ABI 16; kernels: csrc/pcg_rollout_unc.hpp):
+ * parametric uncertainty sampled at reset (nunc > 0), the reference's domain randomisation.  Argument lists, recorded
+ * rows, loop, networks' arithmetic and Philox keys are those of pcg_rollout_policy / pcg_rollout_actor; nothing new is
+ * recorded.  Two things differ:
+ *   - the observation carries nunc more slots, [x | SP | d | unc]: the networks read them (n_in == Nobs of the plan, the
+ *     parameter slots included), and the rows of obs_seq and the final io->obs carry them, as pcg_step writes them;
+ *   - io->p_unc [nunc][B] is read and never written: it is whatever the preceding pcg_reset wrote (pcgym.py:300-316), or
+ *     what the caller placed there.  The lane's folded model constants are rebuilt from it every step, as pcg_step does:
+ *     rebuilding them ONCE per call was built and measured too, is slower as soon as the network has a hidden layer, and
+ *     is not kept.  A call of T steps and T calls of one step return the same bits.
+ * Against a loop over pcg_step the states agree to rounding, not to the bit: the two kernels are compiled separately and
+ * the compiler contracts the model's right-hand side in each on its own (as pcg_rollout and pcg_step differ on such plans).
+ * Plans: built-in models, PCG_INT_RK4, lock-stepped, no constraint rows, fp64 networks.  PCG_E_UNSUPPORTED, before anything
+ * is launched: nunc == 0 (use pcg_rollout_policy / pcg_rollout_actor), ncon > 0, io->t != NULL, any other integrator
+ * (PCG_INT_CV8 refuses per-env parameters at plan creation), a plan with run-time compiled code, a float32 policy, actor or
+ * critic, a model without per-env parameter kernels (the affine registry models).  PCG_E_NULL for io->p_unc == NULL, among
+ * the NULL buffers.  Every other status as in pcg_rollout_policy / pcg_rollout_actor and in their order (policy handle,
+ * sizes, critic, sigma, T / t0, NULL buffers, strides).
+ * Reads the plan, the policies and io->p_unc and writes none of them; no allocation, no memset: safe under stream capture.
+ * Not here: float32 networks, per-env parameters together with constraint rows, PCG_INT_CV8 and the adaptive integrators,
+ * run-time compiled plans, per-env counters. */
+PCG_API int pcg_rollout_policy_unc(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* policy, int32_t t0, int32_t T,
+                                   double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                                   int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                   int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
+PCG_API int pcg_rollout_actor_unc(pcg_plan* plan, const pcg_buffers* io, const pcg_policy* actor, const pcg_policy* critic,
+                                  const double* sigma, int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride,
+                                  int64_t a_comp_stride, double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride,
+                                  double* logp_out, int64_t logp_step_stride, double* value_out, int64_t value_step_stride,
+                                  double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                  int64_t rew_step_stride, int32_t record_next_action, uint64_t seed, void* stream);
 /* Host only: c0 = -(sum_i log sigma_i + na/2 log 2 pi), summed in ascending order in fp64 -- the constant
  * pcg_rollout_actor passes to its kernel.  NaN for a NULL / non-positive / non-finite sigma or na outside 1..PCG_MAX_NA. */
 PCG_API double pcg_actor_logp_const(const double* sigma, int32_t na);

@@ -213,6 +213,8 @@ EXPORTS = [
     "pcg_rollout_actor",
     "pcg_rollout_policy_cons",
     "pcg_rollout_actor_cons",
+    "pcg_rollout_policy_unc",
+    "pcg_rollout_actor_unc",
     "pcg_actor_logp_const",
     "pcg_policy_noise",
     "pcg_step_autoreset",
@@ -294,6 +296,10 @@ def declare(lib):
     lib.pcg_rollout_actor_cons.restype = C.c_int
     lib.pcg_rollout_actor_cons.argtypes = (lib.pcg_rollout_actor.argtypes[:-2] + [vp, C.c_int64, C.c_int64, vp, C.c_int64]
                                            + lib.pcg_rollout_actor.argtypes[-2:])
+    lib.pcg_rollout_policy_unc.restype = C.c_int
+    lib.pcg_rollout_policy_unc.argtypes = list(lib.pcg_rollout_policy.argtypes)
+    lib.pcg_rollout_actor_unc.restype = C.c_int
+    lib.pcg_rollout_actor_unc.argtypes = list(lib.pcg_rollout_actor.argtypes)
     lib.pcg_actor_logp_const.restype = C.c_double
     lib.pcg_actor_logp_const.argtypes = [_pd, C.c_int32]
     lib.pcg_policy_noise.restype = C.c_int

@@ -1887,6 +1887,24 @@ static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   return PCG_OK;
 }
 
+// The entry points for plans WITH per-env parameters (pcg_rollout_policy_unc / _actor_unc): closed_loop_open's checks with the
+// plan's side turned round, as for `cons` -- parameters are required, and what their kernels are not built for (constraint
+// rows, every integrator but RK4, a plan with run-time compiled code, a float32 network, a model without per-env
+// parameter kernels) is refused here, before the sizes
+template <class Fn>
+static int closed_loop_open_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn Kernels::*slot, StepArgs* a, Fn* fn) {
+  PCG_TRY(fill_args(p, io, a));
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  const DevConst& c = p->hc;
+  if (c.nunc <= 0 || c.ncon > 0 || p->jit_fn[0] || io->t || p->integrator_id != PCG_INT_RK4 || q->dtype == PCG_POL_F32)
+    return PCG_E_UNSUPPORTED;
+  *fn = kernels(p->kid).*slot;
+  if (!*fn) return PCG_E_UNSUPPORTED;
+  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  return PCG_OK;
+}
+
 // whether pcg_step on these buffers would take the feature-masked kernel (step_impl's routes, for a lock-stepped built-in
 // plan with rows and without per-env parameters: io->a is the caller's per-step action row, io->d is not given in a closed loop)
 static bool feat_route_of_step(const pcg_plan* p, const pcg_buffers* io) {
@@ -1900,13 +1918,14 @@ static bool feat_route_of_step(const pcg_plan* p, const pcg_buffers* io) {
 template <class Fn, class HeadArgs>
 static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, Fn fn, const HeadArgs& head, const ClosedLoopRun& r,
                               std::initializer_list<SeqRec> head_recs, int f32, int late_status, void* stream,
-                              const ConsRec* cons = nullptr) {
+                              const ConsRec* cons = nullptr, bool unc = false) {
   const DevConst& c = p->hc;
   if (r.T < 1 || r.t0 < 0 || (int64_t)r.t0 + (int64_t)r.T > 0x7fffffffLL) return PCG_E_VALUE;
   if (io->B == 0) return PCG_OK;
   if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
   if ((c.flags & PCG_F_A_DELTA) && !io->a_save) return PCG_E_NULL;
   if ((c.flags & PCG_F_REWARD_TRACK) && !io->u_prev) return PCG_E_NULL;
+  if (unc && !io->p_unc) return PCG_E_NULL;  // (the entry points for plans with per-env parameters: what the reset wrote)
   if (r.obs_seq && r.obs_cs < io->B) return PCG_E_DIM;
   for (const SeqRec& h : head_recs)
     if (h.seq && h.comp_stride < io->B) return PCG_E_DIM;
@@ -1991,6 +2010,21 @@ int pcg_rollout_policy_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
   return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, 0, PCG_OK, stream, &rec);
+}
+
+int pcg_rollout_policy_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
+                           int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
+                           int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
+                           uint64_t seed, void* stream) {
+  StepArgs a;
+  PolFn fn;
+  PCG_TRY(closed_loop_open_unc<PolFn>(p, io, q, &Kernels::roll_policy_unc, &a, &fn));
+  PolicyArgs pa;
+  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
+  pa.record_next = record_next_action ? 1 : 0;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, 0, PCG_OK, stream, nullptr, true);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {
@@ -2087,6 +2121,42 @@ int pcg_rollout_actor_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy*
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
   return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, 0, PCG_OK, stream, &rec);
+}
+
+int pcg_rollout_actor_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, const pcg_policy* v, const double* sigma,
+                          int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                          double* u_seq_out, int64_t u_step_stride, int64_t u_comp_stride, double* logp_out,
+                          int64_t logp_step_stride, double* value_out, int64_t value_step_stride, double* obs_seq,
+                          int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                          int32_t record_next_action, uint64_t seed, void* stream) {
+  StepArgs a;
+  ActFn fn;
+  PCG_TRY(closed_loop_open_unc<ActFn>(p, io, q, &Kernels::roll_actor_unc, &a, &fn));
+  const DevConst& c = p->hc;
+  if (v) {
+    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
+    if (v->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;  // (the kernels for per-env parameters are built for fp64 networks)
+    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
+    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
+  }
+  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
+  if (!sigma) return PCG_E_NULL;
+  for (int i = 0; i < c.na; ++i)
+    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  ActorArgs aa;
+  std::memset(&aa, 0, sizeof(aa));
+  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
+  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
+  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
+  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
+  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
+  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
+  aa.c0 = pcg_actor_logp_const(sigma, c.na);
+  aa.record_next = record_next_action ? 1 : 0;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, 0, PCG_OK, stream, nullptr,
+                            true);
 }
 
 int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {

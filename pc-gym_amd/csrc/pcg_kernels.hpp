@@ -1156,6 +1156,8 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_policy_f32.hpp"
 // (... nor the kernels of the plans with constraint rows: such a plan with run-time compiled code steps)
 #include "pcg_rollout_cons.hpp"
+// (... nor those of the plans with per-env parameters, which refuse run-time compiled code at creation)
+#include "pcg_rollout_unc.hpp"
 #endif
 namespace pcg {
 
@@ -1221,6 +1223,8 @@ struct Kernels {
   ActFn roll_actor_f32[2];
   PolConsFn roll_policy_cons[2];     // the fp64 two on plans with constraint rows, recording the rows (pcg_rollout_cons.hpp)
   ActConsFn roll_actor_cons[2];
+  PolFn roll_policy_unc;             // the fp64 two on plans with per-env parameters (RK4; null for affine: pcg_rollout_unc.hpp)
+  ActFn roll_actor_unc;
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1339,6 +1343,8 @@ Kernels make_kernels() {
     k.step_unc[PCG_INT_DOPRI5][1] = step_kernel<M, PCG_INT_DOPRI5, true, false, true, true>;
     k.rollout_unc[PCG_INT_RK4] = rollout_kernel<M, PCG_INT_RK4, false, true>;
     k.rollout_unc[PCG_INT_DOPRI5] = rollout_kernel<M, PCG_INT_DOPRI5, false, true>;
+    k.roll_policy_unc = rollout_unc_policy_kernel<M>;
+    k.roll_actor_unc = rollout_unc_actor_kernel<M>;
   }
   if constexpr (M::FULL) {
     // DOPRI5 with the stage vectors in LDS (PCG_OPT_LDS_STAGES)

@@ -439,6 +439,48 @@ class VecEnv:
         return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq, "g": g_seq,
                 "viol": viol.view(_torch().bool) if viol is not None else None}
 
+    def rollout_policy_unc(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
+                           record_next_action=False):
+        """``rollout_policy`` on a plan WITH per-env parameters (``pcg_rollout_policy_unc``): the same launch and the same
+        returns; the observation rows (and the policy's input) carry the ``nunc`` parameter slots.  ``env.p_unc`` -- what the
+        last reset sampled -- is read and left as it is.
+        Plans the kernel does not take (no per-env parameters, constraint rows, integrators other than rk4) and float32
+        policies raise PcgError."""
+        if self.per_env_t:
+            raise ValueError("rollout_policy_unc() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_policy_unc(
+            self._plan, self._bufp, policy.handle(dev), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_policy_unc")
+        self.t += T
+        return a_seq, obs_seq, rew_seq
+
+    def rollout_actor_unc(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
+                          collect_logp=True, collect_values=True, record_next_action=False):
+        """``rollout_actor`` on a plan WITH per-env parameters (``pcg_rollout_actor_unc``): its dict, the observation rows with
+        the parameter slots, as ``rollout_policy_unc`` records them; float64 networks only."""
+        if self.per_env_t:
+            raise ValueError("rollout_actor_unc() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
+            ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_actor_unc(
+            self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
+            ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
+            _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_actor_unc")
+        self.t += T
+        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
+
     def policy_noise(self, t=None, out=None):
         """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the
         current episode -- same Philox keys, same bits -- for a caller that samples outside the kernel."""

@@ -241,6 +241,16 @@ def fused_cons_ok(spec, policy):
             and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
 
 
+def fused_unc_ok(spec, policy):
+    """the plans pcg_rollout_policy_unc takes (include/pcgym_hip.h): per-env model parameters sampled at reset (``nunc``), RK4, no
+    constraint rows, built-in plans only (per-env parameters are refused on run-time compiled ones when the spec is made), a
+    float64 policy of the plan's sizes -- whose input counts the parameter slots of the observation.  The collectors take the
+    call with ``fused_unc=True``; their default route on such a plan stays the per-step loop."""
+    return (isinstance(policy, MLPPolicy) and spec.integrator == "rk4" and bool(spec.nunc) and not spec.ncon
+            and not _runtime_compiled(spec) and policy.dtype != "float32"
+            and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
+
+
 def _runtime_compiled(spec):
     """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
     return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)
@@ -385,4 +395,11 @@ def fused_actor_cons_ok(spec, ac):
     """the plans and networks pcg_rollout_actor_cons takes: those of pcg_rollout_policy_cons for the actor, no tanh map, and a
     float64 critic (if any) of the plan's observation size that the device form can hold"""
     return (isinstance(ac, GaussianActorCritic) and fused_cons_ok(spec, ac.actor) and ac.actor.out_map != "tanh"
+            and (ac.critic is None or (ac.critic.n_in == spec.nobs and ac.critic.dtype != "float32" and ac.critic.validate() == 0)))
+
+
+def fused_actor_unc_ok(spec, ac):
+    """the plans and networks pcg_rollout_actor_unc takes: those of pcg_rollout_policy_unc for the actor, no tanh map, and a
+    float64 critic (if any) of the plan's observation size that the device form can hold"""
+    return (isinstance(ac, GaussianActorCritic) and fused_unc_ok(spec, ac.actor) and ac.actor.out_map != "tanh"
             and (ac.critic is None or (ac.critic.n_in == spec.nobs and ac.critic.dtype != "float32" and ac.critic.validate() == 0)))

@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .policy import fused_actor_cons_ok, fused_actor_ok, fused_cons_ok, fused_policy_ok
+from .policy import fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_unc_ok
 
 
 def _torch():
@@ -71,7 +71,7 @@ def _recording(env):
         env.rew.copy_(last_r)
 
 
-def collect_rollouts(env, policy=None, actions=None):
+def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
     """Roll all B envs of a VecEnv through one episode (N-1 steps) and return the reference-shaped dict.
 
     policy  : callable obs(B,Nobs) -> action (B,na)|(na,B) tensor (closed loop); an ``MLPPolicy`` is evaluated inside
@@ -80,6 +80,10 @@ def collect_rollouts(env, policy=None, actions=None):
               WITH affine constraint rows, whose rows the kernel of ``pcg_rollout_policy_cons`` records into ``g``) and
               like any other callable otherwise, or
     actions : (N, na, B) tensor of policy outputs (open loop; row N-1 is only recorded in ``u``).
+    fused_unc : True takes ``pcg_rollout_policy_unc`` -- the whole episode in one launch -- on a built-in RK4 plan with per-env
+              parameters, and raises ValueError unless ``fused_unc_ok(spec, policy)``.  It has to be asked for: by default such a
+              plan keeps the per-step loop, whose results the fused kernel matches to rounding and not to the bit (the two
+              kernels are compiled separately).
 
     Recording is zero-copy: each step's kernel writes its observation / reward rows straight into the trajectory
     storage (``VecEnv.bind_outputs``), and the de-normalisation to physical units (policy_evaluation.py:88-106) is one
@@ -113,6 +117,8 @@ def collect_rollouts(env, policy=None, actions=None):
         actions = actions.to(device=dev, dtype=f64)
         if actions.shape != (N, s.na, B):
             raise ValueError(f"actions must have shape ({N},{s.na},{B})")
+    if fused_unc and (policy is None or not fused_unc_ok(s, policy)):  # (closed loop only: `actions` comes without a policy)
+        raise ValueError("fused_unc: this plan / policy does not qualify for pcg_rollout_policy_unc (fused_unc_ok; closed loop only)")
     if actions is not None and fused_ok:
         # fused: the kernel writes the observation rows directly into x[:, 1:, :] / r[0, 1:, :]
         x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
@@ -154,6 +160,19 @@ def collect_rollouts(env, policy=None, actions=None):
         env.t += N - 1
         g[:, 0, 0] = env.g_pre
         return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0), "g": g}
+    if fused_unc:
+        # the same on a plan with per-env parameters (pcg_rollout_policy_unc), on request: the reset above sampled them; the
+        # observation rows carry the parameter slots, as those of the open-loop collector do
+        x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
+        u = torch.empty((s.na, N, B), dtype=f64, device=dev)
+        x[:, 0] = env.obs_soa
+        env._buf.d = None
+        rc = env._lib.pcg_rollout_policy_unc(
+            env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
+            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_policy_unc")
+        env.t += N - 1
+        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
     # per-step path: step-major storage, the env's kernels write into it
     xs = torch.empty((N, s.nobs, B), dtype=f64, device=dev)
     us = torch.empty((N, s.na, B), dtype=f64, device=dev)
@@ -202,7 +221,7 @@ def gae(rew, val, gamma=0.99, lam=0.95, bootstrap_last=False):
     return adv, adv + val[:T]
 
 
-def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None, record_cons=False):
+def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None, record_cons=False, fused_unc=False):
     """One episode (N - 1 steps) of all B envs under the stochastic actor-critic ``ac`` (a
     :class:`~pcgym_amd.policy.GaussianActorCritic` with a critic): what an on-policy trainer such as PPO collects.
 
@@ -217,6 +236,10 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
     Route: ONE launch (``pcg_rollout_actor``) when the plan and the networks qualify (``fused_actor_ok``: RK4 / CV8, no
     constraint rows, no per-env parameters, no tanh map; user models and reward expressions included); otherwise -- or with ``fused=False`` -- one
     ``env.step`` per step with the sample formed in torch from ``env.policy_noise``, i.e. from the same random bits.
+    ``fused_unc=True`` takes ``pcg_rollout_actor_unc`` -- one launch -- on a built-in RK4 plan with per-env parameters and raises
+    ValueError unless ``fused_actor_unc_ok`` (float64 networks; not with ``record_cons`` or ``fused=False``).  It has to be asked
+    for: by default, and under ``fused``, such a plan keeps the per-step route, whose results the fused kernel matches to
+    rounding and not to the bit.
 
     ``record_cons=True`` (plans with constraint rows only, ValueError otherwise) adds what a constrained trainer needs -- a
     cost signal, a Lagrangian term, a mask after ``done_on_cons_vio``:
@@ -245,7 +268,11 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
     obs[0] = env.obs_soa
     if record_cons and not s.ncon:
         raise ValueError("record_cons: this plan has no constraint rows")
-    ok = fused_actor_cons_ok(s, ac) if record_cons else fused_actor_ok(s, ac)
+    # a plan with per-env parameters: pcg_rollout_actor_unc, on request only (the default route of such a plan stays the step loop)
+    unc = bool(fused_unc)
+    if unc and (record_cons or fused is False or not fused_actor_unc_ok(s, ac)):
+        raise ValueError("fused_unc: this plan / actor-critic does not qualify for pcg_rollout_actor_unc (fused_actor_unc_ok)")
+    ok = fused_actor_cons_ok(s, ac) if record_cons else (unc or fused_actor_ok(s, ac))
     if fused and not ok:
         raise ValueError("this plan / actor-critic does not qualify for the fused call")
     cons = {}
@@ -268,11 +295,12 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
         # (row N-1 of the samples is drawn and dropped: only its value, the bootstrap value, is kept)
         u = torch.empty((N, s.na, B), dtype=f64, device=dev)
         env._buf.d = None
-        rc = env._lib.pcg_rollout_actor(
+        name = "pcg_rollout_actor_unc" if unc else "pcg_rollout_actor"
+        rc = getattr(env._lib, name)(
             env._plan, env._bufp, ac.actor.handle(dev), ac.critic.handle(dev), ac.sigma.ctypes.data_as(C.POINTER(C.c_double)),
             0, T, None, 0, 0, u.data_ptr(), s.na * B, B, logp.data_ptr(), B, val.data_ptr(), B,
             obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, env._episode_seed(), env._stream())
-        _lib.check(rc, "pcg_rollout_actor")
+        _lib.check(rc, name)
         env.t += T
         act = u[:T]
     else:

@@ -17,6 +17,9 @@ With --constraints the workload is the constraint showcase (scenario cstr_cons_p
 alternate: ac = collect_onpolicy(env, ac, record_cons=True), fused (pcg_rollout_actor_cons: rows and flags of every step
 recorded); bc = the same with fused=False, its per-step route; au = collect_onpolicy fused on the unconstrained cstr_canonical
 under rk4, the reference for what the 8 * ncon + 1 recorded bytes per env step cost.
+With --per-env-params the workload is bench.py's cstr_unc (UA, Caf ~ U(+-5 %) sampled per env at reset) and three routes
+alternate: a = collect_onpolicy fused (pcg_rollout_actor_unc), b = the same with fused=False on the same plan, c =
+collect_onpolicy fused on the headline's envs without uncertain parameters.
 With --dtype float32 three routes alternate instead: a32 = collect_onpolicy fused with float32 networks, a64 = the same with
 float64 networks of the same (rounded) weights, b32 = the per-step route of the float32 networks.
 """
@@ -133,6 +136,45 @@ def cons_rows(a, VecEnv, collect_onpolicy, torch):
     return lines
 
 
+def unc_rows(a, bench, VecEnv, collect_onpolicy, torch):
+    p_unc, p_ref = bench.single_workload("cstr_unc")[1], bench.workload_params()
+    lines = ["# --per-env-params: bench.py's cstr_unc (UA, Caf ~ U(+-5 %) per env): a = collect_onpolicy fused (pcg_rollout_actor_unc), "
+             "b = its per-step route on the same plan, c = collect_onpolicy fused on the headline's envs without uncertain parameters"]
+    for name in a.shapes.split(","):
+        envs = {"a": VecEnv(dict(p_unc), n_envs=a.B, seed=1), "b": VecEnv(dict(p_unc), n_envs=a.B, seed=1), "c": VecEnv(dict(p_ref), n_envs=a.B, seed=1)}
+        spec, spec_c = envs["a"].spec, envs["c"].spec
+        assert spec.nunc == 2 and not spec_c.nunc and (spec_c.nobs + spec.nunc, spec_c.na, spec_c.N) == (spec.nobs, spec.na, spec.N)
+        ac, ac_c = make_ac(spec, SHAPES[name]), make_ac(spec_c, SHAPES[name])
+        steps = spec.N - 1
+        routes = {"a": lambda: collect_onpolicy(envs["a"], ac, fused_unc=True), "b": lambda: collect_onpolicy(envs["b"], ac, fused=False),
+                  "c": lambda: collect_onpolicy(envs["c"], ac_c)}
+        times = {k: [] for k in routes}
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        verdict = "fused faster than per-step" if med["a"] < med["b"] else "FUSED NOT FASTER THAN PER-STEP"
+        lines.append(f"{name:7s} a {us['a']:8.2f}  b {us['b']:8.2f}  c {us['c']:8.2f} us/step   b / a = {med['b'] / med['a']:.2f}   a / c = {med['a'] / med['c']:.3f}   "
+                     f"{a.B * steps / med['a'] / 1e-3:.3e} env-steps/s fused   FMAs per env step: actor {policy_fmas(ac.actor)}, critic "
+                     f"{policy_fmas(ac.critic)}   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        ac.close(), ac_c.close()
+        del envs
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
@@ -140,10 +182,13 @@ def main():
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--constraints", action="store_true", help="the constraint showcase: fused-cons against per-step (and the unconstrained fused call)")
+    ap.add_argument("--per-env-params", action="store_true", help="bench.py's cstr_unc: fused-unc against per-step (and the fused call without parameters)")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.constraints and a.dtype != "float64":
         ap.error("--constraints: the constrained kernels take float64 networks")
+    if a.per_env_params and (a.dtype != "float64" or a.constraints):
+        ap.error("--per-env-params: float64 networks, no constraint rows")
     import torch
 
     import bench
@@ -161,7 +206,9 @@ def main():
         lines += f32_rows(a, p, VecEnv, collect_onpolicy, torch)
     if a.constraints:
         lines = lines[:1] + cons_rows(a, VecEnv, collect_onpolicy, torch)
-    for name in ([] if a.dtype == "float32" or a.constraints else a.shapes.split(",")):
+    if a.per_env_params:
+        lines = lines[:1] + unc_rows(a, bench, VecEnv, collect_onpolicy, torch)
+    for name in ([] if a.dtype == "float32" or a.constraints or a.per_env_params else a.shapes.split(",")):
         envs = {k: VecEnv(dict(p), n_envs=a.B, seed=1) for k in ("a", "b", "c", "a0")}
         spec = envs["a"].spec
         ac, ac0 = make_ac(spec, SHAPES[name]), make_ac(spec, SHAPES[name], critic=False)

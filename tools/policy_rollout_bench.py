@@ -13,6 +13,10 @@ With --constraints the workload is the constraint showcase (scenario cstr_cons_p
 r_penalty): the fused call is pcg_rollout_policy_cons, which also records the rows of every step into g; the per-step route
 records them from env.g; a third route, the unconstrained fused call on cstr_canonical under rk4, alternates with them as the
 reference for what the rows cost (8 * ncon recorded bytes per env step; the collector does not ask for the flags).
+With --per-env-params the workload is bench.py's cstr_unc (the headline's envs with UA and Caf ~ U(+-5 %) sampled per env at
+reset) and three routes alternate: a = the fused call (pcg_rollout_policy_unc), b = the per-step route on the same plan
+(step_kernel<..., UNC>), c = the existing fused
+call on the headline's envs without uncertain parameters (two observation slots fewer).
 With --dtype float32 three routes alternate: the float32 fused call (rollout_policy_kernel_f32), the float64 fused call on the
 same (float32-rounded) weights, and the per-step route with the float32 callable.
 """
@@ -101,6 +105,45 @@ def f32_rows(a, p, VecEnv, collect_rollouts, torch):
     return lines
 
 
+def unc_rows(a, bench, VecEnv, collect_rollouts, torch):
+    """the per-env-parameter comparison: a / b / c interleaved, us per step"""
+    p_unc, p_ref = bench.single_workload("cstr_unc")[1], bench.workload_params()
+    lines = ["# --per-env-params: bench.py's cstr_unc (UA, Caf ~ U(+-5 %) per env): a = fused (pcg_rollout_policy_unc), b = per-step route on the "
+             "same plan, c = fused (pcg_rollout_policy) on the headline's envs without uncertain parameters"]
+    for name in a.shapes.split(","):
+        envs = {"a": VecEnv(dict(p_unc), n_envs=a.B, seed=1), "b": VecEnv(dict(p_unc), n_envs=a.B, seed=1), "c": VecEnv(dict(p_ref), n_envs=a.B, seed=1)}
+        spec, spec_c = envs["a"].spec, envs["c"].spec
+        assert spec.nunc == 2 and not spec_c.nunc and (spec_c.nobs + spec.nunc, spec_c.na, spec_c.N) == (spec.nobs, spec.na, spec.N)
+        pol, pol_c = make_policy(spec, SHAPES[name]), make_policy(spec_c, SHAPES[name])
+        steps = spec.N - 1
+        routes = {"a": lambda: collect_rollouts(envs["a"], policy=pol, fused_unc=True), "b": lambda: collect_rollouts(envs["b"], policy=lambda o: pol(o)),
+                  "c": lambda: collect_rollouts(envs["c"], policy=pol_c)}
+        times = {k: [] for k in routes}
+        for rep in range(a.reps + 1):  # (round 0 warms every route up)
+            for k, fn in routes.items():
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                ev0.record()
+                d = fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(ev0.elapsed_time(ev1))
+                del d
+        med = {k: statistics.median(v) for k, v in times.items()}
+        us = {k: 1e3 * med[k] / steps for k in med}
+        verdict = "fused faster than per-step" if med["a"] < med["b"] else "FUSED NOT FASTER THAN PER-STEP"
+        lines.append(f"{name:7s} a {us['a']:8.2f}  b {us['b']:8.2f}  c {us['c']:8.2f} us/step   b / a = {med['b'] / med['a']:.2f}   a / c = {med['a'] / med['c']:.3f}   "
+                     f"{a.B * steps / med['a'] / 1e-3:.3e} env-steps/s fused   policy FMAs per env step {policy_fmas(pol)} (c: {policy_fmas(pol_c)})   {verdict}")
+        lines.append("        repeats (ms per episode) " + "  ".join(f"{k} {[round(t, 2) for t in times[k]]}" for k in times))
+        for e in envs.values():
+            e.close()
+        pol.close(), pol_c.close()
+        del envs
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
@@ -108,10 +151,13 @@ def main():
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--constraints", action="store_true", help="the constraint showcase: fused-cons against per-step (and the unconstrained fused call)")
+    ap.add_argument("--per-env-params", action="store_true", help="bench.py's cstr_unc: fused-unc against per-step (and the fused call without parameters)")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.constraints and a.dtype != "float64":
         ap.error("--constraints: the constrained kernels take float64 policies")
+    if a.per_env_params and (a.dtype != "float64" or a.constraints):
+        ap.error("--per-env-params: float64 policies, no constraint rows")
     import torch
 
     import bench
@@ -135,7 +181,9 @@ def main():
                     "unconstrained fused call on cstr_canonical, rk4; ms per episode, median of the interleaved repeats")
     if a.dtype == "float32":
         lines += f32_rows(a, p, VecEnv, collect_rollouts, torch)
-    for name in ([] if a.dtype == "float32" else a.shapes.split(",")):
+    if a.per_env_params:
+        lines = lines[:1] + unc_rows(a, bench, VecEnv, collect_rollouts, torch)
+    for name in ([] if a.dtype == "float32" or a.per_env_params else a.shapes.split(",")):
         e_f, e_s = VecEnv(dict(p), n_envs=a.B, seed=1), VecEnv(dict(p), n_envs=a.B, seed=1)
         spec = e_f.spec
         pol = make_policy(spec, SHAPES[name])
