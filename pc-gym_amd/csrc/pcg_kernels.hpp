@@ -685,6 +685,30 @@ PCG_DEV void env_pre(const StepArgs& A, CDevConst& c, const double* sched_l, int
     pre.done_pre = v && (flags & PCG_F_DONE_ON_CONS);
   }
 }
+// The three accumulating terms of the declarative tracking reward as exactly specified operation sequences (no contraction),
+// shared by every kernel that states the reward: env_post, env_step_feat (pcg_step_feat.hpp) and env_post_cons
+// (pcg_rollout_cons.hpp).  Under the compiler's default contraction each restatement of `cost += a * b` became an FMA or a
+// multiply and an add kernel by kernel: rollout_cons_actor_kernel<cstr, RK4> and the feature-masked step kernel gave tracking
+// rewards that differ in the last bit, where pcg_rollout_cons.hpp promises the per-step route's bits.  The order is the
+// oracle's (pcg_oracle.c: one `cost +=` per term).  What these take as arguments -- the normalisations (v - lo) * inv, a
+// subtraction followed by a multiplication -- has nothing to fuse; the rest of each restatement is not covered by this.
+PCG_DEV double track_sp_cost(double cost, double xn, double sn, double r_scale) {
+#pragma clang fp contract(off)
+  const double d = xn - sn;
+  return cost + (d * d) * r_scale;
+}
+PCG_DEV double track_act_cost(double cost, double R_du, double R_u, double un, double upn) {
+#pragma clang fp contract(off)
+  const double d = un - upn;
+  cost = cost + R_du * (d * d);
+  return cost + R_u * (un * un);
+}
+PCG_DEV double track_box_cost(double cost, double xn, double lon, double hin) {
+#pragma clang fp contract(off)
+  if (xn > hin) return cost + (xn - hin) * (xn - hin);
+  if (xn < lon) return cost + (lon - xn) * (lon - xn);
+  return cost;
+}
 
 // ---- second half of make_env.step (pcgym.py:432-498): SP slot, constraints, done, reward, observation ----
 // `x` is the integrated state, `status` what the integrator reported for this env.
@@ -782,7 +806,7 @@ PCG_DEV void env_post(const StepArgs& A, CDevConst& c, const double* sched_l, in
         }
         const double xn = (xv - c.trk_lo[k]) * c.trk_inv[k];
         const double sn = (spn[k] - c.trk_lo[k]) * c.trk_inv[k];
-        cost += ((xn - sn) * (xn - sn)) * c.r_scale[k];
+        cost = track_sp_cost(cost, xn, sn, c.r_scale[k]);
       }
 #pragma unroll
     for (int j = 0; j < NA; ++j)
@@ -791,14 +815,13 @@ PCG_DEV void env_post(const StepArgs& A, CDevConst& c, const double* sched_l, in
         const double up = (up0 == up0) ? up0 : u[j];  // NaN: no previous action yet (hasattr branch, :7-8)
         const double un = (u[j] - c.act_lo[j]) * c.act_inv[j];
         const double upn = (up - c.act_lo[j]) * c.act_inv[j];
-        cost += c.R_du * ((un - upn) * (un - upn)) + c.R_u * (un * un);
+        cost = track_act_cost(cost, c.R_du, c.R_u, un, upn);
         A.u_prev[(size_t)j * B + e] = u[j];
       }
     if (violated)
       for (int q = 0; q < c.nbox; ++q) {
         const double xn = (pick<NX>(on, c.box_index[q]) - c.box_lo[q]) * c.box_inv[q];
-        if (xn > c.box_hin[q]) cost += (xn - c.box_hin[q]) * (xn - c.box_hin[q]);
-        else if (xn < c.box_lon[q]) cost += (c.box_lon[q] - xn) * (c.box_lon[q] - xn);
+        cost = track_box_cost(cost, xn, c.box_lon[q], c.box_hin[q]);
       }
     out.rew = -cost;
   }

@@ -19,9 +19,10 @@
 // from viol_seq.
 //
 // The step is env_pre -> integrate_env -> env_post_cons; env_post_cons restates env_post<M, false, true> with the rows taken
-// from cons_rows (env_step, env_post and constraint_rows keep their text, and no kernel that existed before this header
-// changes).  env_pre's own pre-step check runs with a null g_pre and its verdict is replaced.  The loops are restated and not
-// shared with the unconstrained kernels for the reason pcg_rollout_policy.hpp gives.
+// from cons_rows (env_step and constraint_rows keep their text; the terms of the tracking reward are the contraction-free
+// track_*_cost of pcg_kernels.hpp in env_post, env_step_feat and here, which is what makes its bits the per-step route's).
+// env_pre's own pre-step check runs with a null g_pre and its verdict is replaced.  The loops are restated and not shared
+// with the unconstrained kernels for the reason pcg_rollout_policy.hpp gives.
 //
 // Out of scope: constraint expressions and user models (their run-time compiled closed-loop module carries the two
 // unconstrained kernels only), float32 networks, per-env parameters, adaptive integrators, and the open-loop pcg_rollout*
@@ -166,7 +167,7 @@ PCG_DEV void env_post_cons(const StepArgs& A, CDevConst& c, const ConsArgs& G, i
         }
         const double xn = (xv - c.trk_lo[k]) * c.trk_inv[k];
         const double sn = (spn[k] - c.trk_lo[k]) * c.trk_inv[k];
-        cost += ((xn - sn) * (xn - sn)) * c.r_scale[k];
+        cost = track_sp_cost(cost, xn, sn, c.r_scale[k]);
       }
 #pragma unroll
     for (int j = 0; j < NA; ++j)
@@ -175,14 +176,13 @@ PCG_DEV void env_post_cons(const StepArgs& A, CDevConst& c, const ConsArgs& G, i
         const double up = (up0 == up0) ? up0 : u[j];  // NaN: no previous action yet
         const double un = (u[j] - c.act_lo[j]) * c.act_inv[j];
         const double upn = (up - c.act_lo[j]) * c.act_inv[j];
-        cost += c.R_du * ((un - upn) * (un - upn)) + c.R_u * (un * un);
+        cost = track_act_cost(cost, c.R_du, c.R_u, un, upn);
         A.u_prev[(size_t)j * B + e] = u[j];
       }
     if (violated)
       for (int q = 0; q < c.nbox; ++q) {
         const double xn = (pick<NX>(on, c.box_index[q]) - c.box_lo[q]) * c.box_inv[q];
-        if (xn > c.box_hin[q]) cost += (xn - c.box_hin[q]) * (xn - c.box_hin[q]);
-        else if (xn < c.box_lon[q]) cost += (c.box_lon[q] - xn) * (c.box_lon[q] - xn);
+        cost = track_box_cost(cost, xn, c.box_lon[q], c.box_hin[q]);
       }
     out.rew = -cost;
   }

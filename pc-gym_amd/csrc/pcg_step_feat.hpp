@@ -232,7 +232,8 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
         if (k < nsp) {
           const R xn = (pick<NX, W>(on, c.sp_index[k]) - c.trk_lo[k]) * c.trk_inv[k];
           const double sn = (spn[k] - c.trk_lo[k]) * c.trk_inv[k];
-          cost = cost + ((xn - sn) * (xn - sn)) * c.r_scale[k];
+#pragma unroll
+          for (int j = 0; j < W; ++j) cost.v[j] = track_sp_cost(cost.v[j], xn.v[j], sn, c.r_scale[k]);
         }
 #pragma unroll
       for (int q = 0; q < NA; ++q) {
@@ -242,7 +243,8 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
           up.v[j] = (uprev_in[q].v[j] == uprev_in[q].v[j]) ? uprev_in[q].v[j] : u[q].v[j];
         const R un = (u[q] - c.act_lo[q]) * c.act_inv[q];
         const R upn = (up - c.act_lo[q]) * c.act_inv[q];
-        cost = cost + c.R_du * ((un - upn) * (un - upn)) + c.R_u * (un * un);
+#pragma unroll
+        for (int j = 0; j < W; ++j) cost.v[j] = track_act_cost(cost.v[j], c.R_du, c.R_u, un.v[j], upn.v[j]);
         *reinterpret_cast<typename Vec<W>::T*>(A.u_prev + (size_t)q * B + e0) = Vec<W>::make(u[q].v);
       }
       if constexpr (CONS) {
@@ -250,10 +252,7 @@ PCG_DEV void env_step_feat(const StepArgs& A, CDevConst& c, int64_t e0, int t, c
           const R xn = (pick<NX, W>(on, c.box_index[q]) - c.box_lo[q]) * c.box_inv[q];
 #pragma unroll
           for (int j = 0; j < W; ++j)
-            if (violated[j]) {
-              if (xn.v[j] > c.box_hin[q]) cost.v[j] += (xn.v[j] - c.box_hin[q]) * (xn.v[j] - c.box_hin[q]);
-              else if (xn.v[j] < c.box_lon[q]) cost.v[j] += (c.box_lon[q] - xn.v[j]) * (c.box_lon[q] - xn.v[j]);
-            }
+            if (violated[j]) cost.v[j] = track_box_cost(cost.v[j], xn.v[j], c.box_lon[q], c.box_hin[q]);
         }
       }
       r = -cost;

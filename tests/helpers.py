@@ -217,6 +217,19 @@ def _close(a, b):
     return ((a[fa] - b[fa]).abs() / b[fa].abs().clamp_min(1e-9)).max().item()
 
 
+def _unc_over(model, pick=None):
+    """env_params entries that make `pick` (default: the model's first two non-zero parameters) uncertain: +-3 %, uniform,
+    observed in a box of +-10 %"""
+    from pcgym_amd.models import get_model
+
+    mi = get_model(model)
+    if pick is None:
+        pick = [k for k, v in mi.parameters.items() if float(v) != 0.0 and k not in ("N", "eq_exponent")][:2]
+    return dict(uncertainty_percentages={k: 0.03 for k in pick}, distribution="uniform",
+                uncertainty_bounds={"low": np.array([min(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick]),
+                                    "high": np.array([max(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick])})
+
+
 def _unc_params(key, integ):
     import pytest
     from pcgym_amd.models import get_model
@@ -225,12 +238,8 @@ def _unc_params(key, integ):
     mi = get_model(model)
     if mi.affine_builder is not None:
         pytest.skip("affine registry models have no per-env parameter kernel")
-    names = [k for k, v in mi.parameters.items() if float(v) != 0.0 and k not in ("N", "eq_exponent")]
-    pick = names[:2]
     p = sweep_params(key, integ, "lean")
-    p.update(uncertainty_percentages={k: 0.03 for k in pick}, distribution="uniform",
-             uncertainty_bounds={"low": np.array([min(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick]),
-                                 "high": np.array([max(0.9 * mi.parameters[k], 1.1 * mi.parameters[k]) for k in pick])})
+    p.update(_unc_over(model))
     return p
 
 
@@ -497,6 +506,68 @@ def _spread_x0(p, pct=0.02):
 CASE_KEYS = MODEL_KEYS + ["cstr_noise", "cstr_raw"]
 
 
+# ---- the feature plans of the closed-loop rollouts (tests/test_closed_loop_feature_plans.py proves each case non-vacuous on
+# the oracle alone; tests/test_gpu_closed_loop_features.py runs them through the kernels) ----------------------------------------
+# name -> (scenario of tests/golden/scenarios.py, env_params changes, what the plan is there for).  Kinds:
+#   track    the declarative tracking reward (io->u_prev read and written every step)      box   its box-excess term
+#   cryst    CV and Ln recomputed from the observed moments                                 dist  a disturbance schedule
+#   gauss    Gaussian disturbances on top of the schedule                                   mask  partial observation
+#   batch    the terminal batch reward                                                      noise observation noise
+#   row1     one affine row over the first state and the action, b = the median of its linear part over the oracle's episode
+#   rows8    PCG_MAX_NCON dense rows over a state, the SP slot, every disturbance slot, the action and the model's
+#            disturbance inputs, b_r = the 0.9 quantile of row r's linear part over the oracle's episode
+#   unc      _unc_over's two uncertain model parameters (q11: one of them is read by an unconfigured disturbance input)
+_TRACK_RU = {"kind": "sp_track", "R": 0.1, "R_u": 0.05}  # (R_u defaults to 0, which makes its term vacuous)
+FEATURE_PLANS = {
+    # the base float64 / float32 families
+    "cstr_paper_reward": ("cstr_paper_reward", {}, ("track",)),
+    "four_tank_paper_reward_Ru": ("four_tank_paper_reward", dict(custom_reward=_TRACK_RU), ("track", "R_u")),
+    "cryst_paper_reward": ("cryst_paper_reward", {}, ("track", "cryst")),
+    "cstr_dist_Ti": ("cstr_dist_Ti", {}, ("dist",)),
+    "cstr_dist_both": ("cstr_dist_both", {}, ("dist",)),
+    "cstr_dist_Ti_gauss": ("cstr_dist_Ti", dict(gaussian_disturbances={"Ti": 1.0}), ("dist", "gauss")),
+    "cstr_partial_obs": ("cstr_partial_obs", {}, ("mask",)),
+    "cstr_batch_reward": ("cstr_batch_reward", {}, ("batch",)),
+    # the constrained family
+    "cstr_con_reward": ("cstr_con_reward", {}, ("track", "box", "cons")),
+    "cstr_con_reward_noise": ("cstr_con_reward", dict(noise=True, noise_percentage=0.002), ("track", "box", "noise", "cons")),
+    "cryst_paper_reward_row": ("cryst_paper_reward", {}, ("track", "cryst", "row1", "cons")),
+    "me_dist_cons": ("me_dist_cons", {}, ("dist", "cons")),
+    "cstr_dist_both_rows8": ("cstr_dist_both", {}, ("dist", "rows8", "cons")),
+    # the per-env-parameter family
+    "unc_cstr_paper_reward": ("cstr_paper_reward", {}, ("track", "unc")),
+    "unc_cstr_dist_Ti": ("cstr_dist_Ti", {}, ("dist", "unc")),
+    "unc_cstr_dist_Ti_Caf": ("cstr_dist_Ti", {}, ("dist", "unc", "q11")),
+    "unc_cstr_noise": ("cstr_canonical", dict(noise=True, noise_percentage=0.002), ("noise", "unc")),
+    "unc_cryst_adelta": ("cryst_adelta", {}, ("unc",)),
+    "unc_cstr_partial_obs": ("cstr_partial_obs", {}, ("mask", "unc")),
+}
+BASE_FEATURE_PLANS = [n for n, v in FEATURE_PLANS.items() if "cons" not in v[2] and "unc" not in v[2]]
+CONS_FEATURE_PLANS = [n for n, v in FEATURE_PLANS.items() if "cons" in v[2]]
+UNC_FEATURE_PLANS = [n for n, v in FEATURE_PLANS.items() if "unc" in v[2]]
+Q11_PICK = ["q", "Caf"]  # Caf: a disturbance input of the cstr that cstr_dist_Ti leaves unconfigured
+
+
+def feature_params(name, integ, rows=None):
+    """env_params of feature plan `name` under `integ`, every env with its own initial state (_spread_x0); `rows` = (A, b)
+    of the affine constraint rows of a row1 / rows8 plan (the plan without them while the bounds are being chosen)"""
+    scen, over, kinds = FEATURE_PLANS[name]
+    p = copy.deepcopy(SC.scenarios()[scen]["env_params"])
+    p.update(copy.deepcopy(over))
+    p.update(integrator=integ)
+    if integ == "cv8" and p["model"].startswith("multistage"):
+        p["substeps"] = 256  # (as in sweep_params: the order-8 scheme's own default step is unstable there)
+    _spread_x0(p)
+    if "unc" in kinds:
+        u = _unc_over(p["model"], Q11_PICK if "q11" in kinds else None)
+        u["uncertainty_percentages"].update(p["uncertainty_percentages"])
+        p.update(u)
+    if rows is not None:
+        p.update(constraints={"A": np.asarray(rows[0], dtype=float), "b": np.asarray(rows[1], dtype=float)}, done_on_cons_vio=False,
+                 r_penalty=True)
+    return p
+
+
 def _perm_hidden(pol, seed):
     """the same function with the hidden units in another order (another summation order in every layer after the first)"""
     from pcgym_amd import MLPPolicy
@@ -517,3 +588,50 @@ UNSUPPORTED_PLANS = {
                                                   uncertainty_bounds={"low": np.array([90.0]), "high": np.array([110.0])})),
     "rodas5": ("me_canonical", dict(integrator="rodas5")),
 }
+
+
+# ---- shared by the closed-loop tests on constrained plans and on plans with per-env parameters ------------------------------------
+def _stepped(env, a_seq, T, record_x=True):
+    """the per-step route under the callable policy that replays `a_seq`: dict of stacked per-step results"""
+    torch = _torch()
+    out = {k: [] for k in ("obs", "rew", "g", "viol", "done", "x0")}
+    for s in range(T):
+        if record_x:
+            out["x0"].append(env.x.clone())
+        env.step(a_seq[s])
+        out["obs"].append(env.obs_soa.clone()), out["rew"].append(env.rew.clone()), out["g"].append(env.g.clone())
+        out["viol"].append(env.viol.clone()), out["done"].append(env.done.clone())
+        if s == 0 and env.t == 1:
+            out["g_pre"] = env.g_pre.clone()
+    return {k: (torch.stack(v) if isinstance(v, list) and v else v) for k, v in out.items()}
+
+
+def _check_final(ef, es):
+    torch = _torch()
+    for n in ("x", "obs_soa", "rew", "done", "viol", "g", "g_pre"):
+        assert torch.equal(getattr(ef, n), getattr(es, n)), f"io->{n} after the call is not what the step loop leaves"
+    if ef.spec.a_delta:
+        assert torch.equal(ef.a_save_t, es.a_save_t)
+    if ef.u_prev is not None:
+        assert torch.equal(ef.u_prev, es.u_prev)
+    assert ef.t == es.t
+
+
+def _tols(key):
+    hat = "^" in key
+    return dict(x1=5e-6 if hat else 1e-8, o_rtol=1e-5 if hat else 1e-8, o_atol=1e-5 if hat else 1e-9, xT=2e-5 if hat else 1e-7)
+
+
+def _rew_close(r, ref):
+    return np.allclose(r, ref, rtol=1e-9, atol=1e-10 * (1 + np.max(np.abs(ref))))
+
+
+def _final_equal(ea, eb):
+    torch = _torch()
+    for n in ("x", "obs_soa", "rew", "done", "p_unc"):
+        assert torch.equal(getattr(ea, n), getattr(eb, n)), f"io->{n} after the chunks is not what the single call leaves"
+    if ea.spec.a_delta:
+        assert torch.equal(ea.a_save_t, eb.a_save_t)
+    if ea.u_prev is not None:
+        assert torch.equal(torch.nan_to_num(ea.u_prev, nan=-7.0), torch.nan_to_num(eb.u_prev, nan=-7.0))
+    assert ea.t == eb.t

@@ -101,7 +101,7 @@ def _np_raw(pol, obs):
     return h
 
 
-def host_conditioning(spec, ac, B, T, env_seed):
+def host_conditioning(spec, ac, B, T, env_seed, n_threads=1):
     """The ORACLE's own sensitivity along the case's closed loop, simulated on the host (fp64 numpy actor, the oracle's noise
     twin): the largest change of a step's result, relative to max(|x|, 1), when the step's start state is perturbed by 1e-15
     relative; inf if a state is not finite.  Also the share of clipped samples at the first step.  An explicit step whose
@@ -110,7 +110,7 @@ def host_conditioning(spec, ac, B, T, env_seed):
     meaningful on inputs where this figure is small."""
     from oracle import oracle as O
 
-    o1, o2 = O.OracleEnv(spec, B, seed=env_seed), O.OracleEnv(spec, B, seed=env_seed)
+    o1, o2 = (O.OracleEnv(spec, B, seed=env_seed, n_threads=n_threads) for _ in range(2))
     o1.reset(), o2.reset()
     z = z_twin(o1._seed(), 0, B, spec.na, range(T))
     rng = np.random.default_rng(0)

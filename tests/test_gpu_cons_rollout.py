@@ -23,7 +23,8 @@ import numpy as np
 import pytest
 
 import scenarios as SC
-from helpers import LD, MODEL_KEYS, PRE_MAX, U, _case_params, _launched, _make, _spread_x0, _torch, host_reference, make_policy, tanh_k
+from helpers import (LD, MODEL_KEYS, PRE_MAX, U, _case_params, _check_final, _launched, _make, _spread_x0, _stepped, _torch, host_reference,
+                     make_policy, tanh_k)
 from test_gpu_actor_rollout import logp_numpy, make_ac, pick_ac, raw_twin
 
 pytestmark = pytest.mark.gpu
@@ -93,32 +94,6 @@ def _plan(key, integ, head="policy"):
     env.close(), net.close()
     _PLANS[key, integ, head] = (plan, box)
     return plan, box
-
-
-def _stepped(env, a_seq, T, record_x=True):
-    """the per-step route under the callable policy that replays `a_seq`: dict of stacked per-step results"""
-    torch = _torch()
-    out = {k: [] for k in ("obs", "rew", "g", "viol", "done", "x0")}
-    for s in range(T):
-        if record_x:
-            out["x0"].append(env.x.clone())
-        env.step(a_seq[s])
-        out["obs"].append(env.obs_soa.clone()), out["rew"].append(env.rew.clone()), out["g"].append(env.g.clone())
-        out["viol"].append(env.viol.clone()), out["done"].append(env.done.clone())
-        if s == 0 and env.t == 1:
-            out["g_pre"] = env.g_pre.clone()
-    return {k: (torch.stack(v) if isinstance(v, list) and v else v) for k, v in out.items()}
-
-
-def _check_final(ef, es):
-    torch = _torch()
-    for n in ("x", "obs_soa", "rew", "done", "viol", "g", "g_pre"):
-        assert torch.equal(getattr(ef, n), getattr(es, n)), f"io->{n} after the call is not what the step loop leaves"
-    if ef.spec.a_delta:
-        assert torch.equal(ef.a_save_t, es.a_save_t)
-    if ef.u_prev is not None:
-        assert torch.equal(ef.u_prev, es.u_prev)
-    assert ef.t == es.t
 
 
 def _row_scale(spec, x, sp_d, u_phys):

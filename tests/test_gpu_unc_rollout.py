@@ -18,8 +18,8 @@ import numpy as np
 import pytest
 
 import scenarios as SC
-from helpers import (LD, MODEL_KEYS, PRE_MAX, U, _launched, _make, _torch, _unc_params, host_reference, make_policy, sweep_params, tanh_k,
-                     worst_rel)
+from helpers import (LD, MODEL_KEYS, PRE_MAX, U, _final_equal, _launched, _make, _rew_close, _tols, _torch, _unc_params, host_reference,
+                     make_policy, sweep_params, tanh_k, worst_rel)
 from test_gpu_actor_rollout import logp_numpy, make_ac, pick_ac, raw_twin
 
 pytestmark = pytest.mark.gpu
@@ -42,15 +42,6 @@ def _params(key):
     p = _unc_params(key, "rk4")
     p["uncertainty_percentages"] = dict(p["uncertainty_percentages"], x0=[0.02] * 24)
     return p
-
-
-def _tols(key):
-    hat = "^" in key
-    return dict(x1=5e-6 if hat else 1e-8, o_rtol=1e-5 if hat else 1e-8, o_atol=1e-5 if hat else 1e-9, xT=2e-5 if hat else 1e-7)
-
-
-def _rew_close(r, ref):
-    return np.allclose(r, ref, rtol=1e-9, atol=1e-10 * (1 + np.max(np.abs(ref))))
 
 
 def _envs(p, n, nb=B):
@@ -118,17 +109,6 @@ def test_every_instantiation_against_the_oracle(key, head):
 
 
 # ---- 2. one call equals chunked calls, bit for bit ------------------------------------------------------------------------------------
-def _final_equal(ea, eb):
-    torch = _torch()
-    for n in ("x", "obs_soa", "rew", "done", "p_unc"):
-        assert torch.equal(getattr(ea, n), getattr(eb, n)), f"io->{n} after the chunks is not what the single call leaves"
-    if ea.spec.a_delta:
-        assert torch.equal(ea.a_save_t, eb.a_save_t)
-    if ea.u_prev is not None:
-        assert torch.equal(torch.nan_to_num(ea.u_prev, nan=-7.0), torch.nan_to_num(eb.u_prev, nan=-7.0))
-    assert ea.t == eb.t
-
-
 @pytest.mark.parametrize("head", ["policy", "actor"])
 @pytest.mark.parametrize("nb", [B, 131])
 def test_one_call_equals_chunked_calls_bitwise(nb, head):
@@ -196,17 +176,19 @@ def test_against_the_per_step_route(key, head):
 
 
 # ---- 4. the networks ---------------------------------------------------------------------------------------------------------------------
-def _slot_policy(spec, obs0):
-    """make_policy's network with ONE large first-layer weight on the last parameter slot: a dropped slot shows in the output"""
+def _slot_policy(spec, obs0, slot=None, values=None):
+    """make_policy's network with ONE large first-layer weight on `slot` (default: the last parameter slot): a dropped slot
+    shows in the output.  `values`: what the slot takes (default: over the batch at reset)"""
     from pcgym_amd import MLPPolicy
 
     pol = make_policy(spec, obs0, (16,), seed=17)
     Ws, bs = [w.copy() for w in pol.weights], [b.copy() for b in pol.biases]
-    slot = spec.nobs - 1
-    spread = float(np.max(obs0[slot]) - np.min(obs0[slot]))
+    slot = spec.nobs - 1 if slot is None else slot
+    values = obs0[slot] if values is None else values
+    spread = float(np.max(values) - np.min(values))
     assert spread > 0
     w = 4.0 / spread  # the slot alone moves the unit's pre-activation by 4 across the batch
-    bs[0][0] -= (w - Ws[0][0, slot]) * float(np.mean(obs0[slot]))
+    bs[0][0] -= (w - Ws[0][0, slot]) * float(np.mean(values))
     Ws[0][0, slot] = w
     Ws[1][:, 0] = np.where(Ws[1][:, 0] >= 0, 1.0, -1.0) * max(float(np.max(np.abs(Ws[1]))), 0.1)  # (and the unit reaches the output)
     out = MLPPolicy(Ws, bs, activation=pol.activation, out_map=pol.out_map, out_low=pol.out_low, out_high=pol.out_high)
