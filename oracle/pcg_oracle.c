@@ -1667,6 +1667,10 @@ ORC_EXPORT double orc_rng_normal(uint64_t seed, uint64_t env, uint32_t t, uint32
 ORC_EXPORT double orc_rng_uniform(uint64_t seed, uint64_t env, uint32_t t, uint32_t purpose, int idx) {
   return rng_uniform(seed, env, t, purpose, idx);
 }
+/* box_muller_f32 on n word pairs (tests/test_rng_accuracy.py: the polynomials against a long double Box-Muller) */
+ORC_EXPORT void orc_box_muller_f32_n(const uint32_t* w0, const uint32_t* w1, int64_t n, float* z0, float* z1) {
+  for (int64_t i = 0; i < n; ++i) box_muller_f32(w0[i], w1[i], &z0[i], &z1[i]);
+}
 
 /* ------------------------------------------------------------------------- */
 /* make_env.step for ONE environment, pcgym.py:350-500, statement by statement */

@@ -232,7 +232,9 @@ PCG_DEV void rng_uniform2(uint64_t seed, uint64_t env, uint32_t t, uint32_t stre
 // specified, so the oracle's C twin (fmaf / sqrtf / rintf) produces the SAME BITS, and the variate costs ~65 fp32
 // instructions for two normals instead of ~100 fp64 ones at half the issue rate (the fp64 log / sqrt / sincospi of
 // round 1 made observation noise cost more VALU time than the whole RK4 step: profiles/r1/exploration.md).  A 24-bit
-// uniform and ~1e-7 relative accuracy are far beyond what a noise sample needs (the reference draws np.random.normal).
+// uniform and variates within 2.0e-7 of r (3.4 units of 2^-24 r, measured against a long double Box-Muller on the same
+// uniforms; tests/test_rng_accuracy.py holds 6 units) are far beyond what a noise sample needs (the reference draws
+// np.random.normal).
 //   u0 = odd 24-bit integer * 2^-24 in (0,1),  u1 = 24-bit integer * 2^-24 in [0,1)
 //   ln u0 = e ln2 + 2 atanh(s), s = (m-1)/(m+1), m in [sqrt(1/2), sqrt(2));   r = sqrt(-2 ln u0)
 //   angle 2 pi u1 by quarter turns, Taylor polynomials on [-pi/4, pi/4];   z0 = r cos, z1 = r sin
