@@ -1808,11 +1808,14 @@ int pcg_policy_destroy(pcg_policy* q) {
   return (int)e;
 }
 
-// Both closed-loop entry points validate through these two: closed_loop_open up to the policy's size, then what is the entry
-// point's own (the actor: critic, tanh map, sigma), then closed_loop_launch from the step range on.  (Templates over the
-// kernel's function and argument types: C++ linkage inside this file's extern "C".)
+// All six closed-loop entry points (pcg_rollout_policy / pcg_rollout_actor, their _cons and _unc forms) validate through three
+// functions, read top to bottom: closed_loop_open up to the policy's size, then the head's own (policy_head; actor_head: critic,
+// tanh map, sigma), then closed_loop_launch from the step range on.  (closed_loop_launch is a template over the head's
+// argument type: C++ linkage inside this file's extern "C".)
 extern "C++" {
-struct ClosedLoopRun {  // what both entry points are given beside their networks: step range, the env's recorded sequences, seed
+// the kind of plan an entry point is for: without constraint rows and per-env parameters, WITH rows (recorded per step), WITH parameters
+enum class ClosedLoopKind { base, cons, unc };
+struct ClosedLoopRun {  // what every entry point is given beside its networks: step range, the env's recorded sequences, seed
   int32_t t0, T;
   double* obs_seq;
   int64_t obs_ss, obs_cs;  // element strides (step, component)
@@ -1824,7 +1827,7 @@ struct SeqRec {  // a sequence the head records, with its component stride; null
   const double* seq;
   int64_t comp_stride;
 };
-struct ConsRec {  // what the constrained entry points record beside: rows [T][ncon][B]-like, flags [T][B]-like
+struct ConsRec {  // what ClosedLoopKind::cons adds: the rows [T][ncon][B]-like and flags [T][B]-like its entry points record
   double* g_seq;
   int64_t g_ss, g_cs;
   uint8_t* viol_seq;
@@ -1859,49 +1862,87 @@ static int jit_prepare_closed_loop(pcg_plan* p) {
 static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return p->jit_pol; }
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
 
-// `cons`: the entry points for plans WITH constraint rows (pcg_rollout_policy_cons / _actor_cons: table_f32 is null) -- the
-// same checks with the plan's side turned round: rows are required, and what their kernels are not built for (a plan with
-// run-time compiled code, a float32 network) is refused here, before the sizes
-template <class Fn>
-static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn (Kernels::*table)[2],
-                            Fn (Kernels::*table_f32)[2], StepArgs* a, Fn* fn, bool cons = false) {
+// Plan, buffers and policy handle; then which plans the kind's kernels carry and which kernel it is (`actor`: the head); then
+// the policy's sizes.  *fn stays null for a plan with run-time compiled code, which has no ahead-of-time kernel:
+// closed_loop_launch takes its own module's.
+static int closed_loop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, ClosedLoopKind kind, bool actor, StepArgs* a,
+                            const void** fn) {
   PCG_TRY(fill_args(p, io, a));
   if (!q) return PCG_E_NULL;
   if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
   const DevConst& c = p->hc;
-  // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, and every integrator
-  // but the two fixed-step schemes
+  const Kernels& k = kernels(p->kid);
   const int ls = lean_scheme(p->integrator_id);
-  if (cons) {
-    if (c.ncon <= 0 || p->jit_fn[0] || io->t || c.nunc > 0 || ls < 0 || q->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;
-    *fn = (kernels(p->kid).*table)[ls];
-    if (!*fn) return PCG_E_UNSUPPORTED;
-    if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
-    return PCG_OK;
+  const bool jit = p->jit_fn[0] != nullptr, f32 = q->dtype == PCG_POL_F32;
+  *fn = nullptr;
+  switch (kind) {
+    case ClosedLoopKind::base:
+      // what the closed-loop kernels do not carry: per-env counters, constraint rows, per-env parameters, and every integrator
+      // but the two fixed-step schemes
+      if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
+      if (!jit)
+        *fn = actor ? (const void*)(f32 ? k.roll_actor_f32 : k.roll_actor)[ls] : (const void*)(f32 ? k.roll_policy_f32 : k.roll_policy)[ls];
+      break;
+    case ClosedLoopKind::cons:
+      // the plan's side turned round: rows are required, and what these kernels are not built for (a plan with run-time
+      // compiled code, a float32 network) is refused here, before the sizes
+      if (c.ncon <= 0 || jit || io->t || c.nunc > 0 || ls < 0 || f32) return PCG_E_UNSUPPORTED;
+      *fn = actor ? (const void*)k.roll_actor_cons[ls] : (const void*)k.roll_policy_cons[ls];
+      break;
+    case ClosedLoopKind::unc:
+      // likewise: parameters are required; no constraint rows, RK4 alone, and (the null entry) a model with kernels for them
+      if (c.nunc <= 0 || c.ncon > 0 || jit || io->t || p->integrator_id != PCG_INT_RK4 || f32) return PCG_E_UNSUPPORTED;
+      *fn = actor ? (const void*)k.roll_actor_unc : (const void*)k.roll_policy_unc;
+      break;
   }
-  if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
-  // (a run-time compiled plan has no ahead-of-time kernel: closed_loop_launch takes its own module's)
-  *fn = p->jit_fn[0] ? nullptr : (kernels(p->kid).*(q->dtype == PCG_POL_F32 ? table_f32 : table))[ls];
-  if (!*fn && !p->jit_fn[0]) return PCG_E_UNSUPPORTED;
+  if (!*fn && !jit) return PCG_E_UNSUPPORTED;
   if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
   return PCG_OK;
 }
 
-// The entry points for plans WITH per-env parameters (pcg_rollout_policy_unc / _actor_unc): closed_loop_open's checks with the
-// plan's side turned round, as for `cons` -- parameters are required, and what their kernels are not built for (constraint
-// rows, every integrator but RK4, a plan with run-time compiled code, a float32 network, a model without per-env
-// parameter kernels) is refused here, before the sizes
-template <class Fn>
-static int closed_loop_open_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, Fn Kernels::*slot, StepArgs* a, Fn* fn) {
-  PCG_TRY(fill_args(p, io, a));
-  if (!q) return PCG_E_NULL;
-  if (q->magic != POLICY_MAGIC || q->device != p->device) return PCG_E_PLAN;
+// what the base kind, the one that takes float32 networks, refuses after every other check (closed_loop_launch): float32 on
+// a plan with run-time compiled code, whose closed-loop module carries the fp64 kernels alone
+static int f32_on_jit(const pcg_plan* p, const pcg_policy* q) {
+  return q->dtype == PCG_POL_F32 && p->jit_fn[0] ? PCG_E_UNSUPPORTED : PCG_OK;
+}
+
+static PolicyArgs policy_head(const pcg_policy* q, double* a_out, int64_t ao_ss, int64_t ao_cs, int32_t record_next) {
+  PolicyArgs pa;
+  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  pa.a_out = a_out; pa.ao_ss = ao_ss; pa.ao_cs = ao_cs;
+  pa.record_next = record_next ? 1 : 0;
+  return pa;
+}
+
+// The actor's own checks, after closed_loop_open's, and its kernel argument: critic (handle; its dtype for `cons` / `unc`,
+// whose kernels are built for fp64 networks; sizes; map), tanh-mapped actor, sigma.  *late: the base kind evaluates both
+// networks in one kernel of one dtype -- an actor and a critic of two dtypes are refused, but after every other check.
+static int actor_head(const pcg_plan* p, ClosedLoopKind kind, const pcg_policy* q, const pcg_policy* v, const double* sigma,
+                      double* a_out, int64_t ao_ss, int64_t ao_cs, double* u_out, int64_t uo_ss, int64_t uo_cs, double* lp_out,
+                      int64_t lp_ss, double* v_out, int64_t v_ss, int32_t record_next, ActorArgs* aa, int* late) {
   const DevConst& c = p->hc;
-  if (c.nunc <= 0 || c.ncon > 0 || p->jit_fn[0] || io->t || p->integrator_id != PCG_INT_RK4 || q->dtype == PCG_POL_F32)
-    return PCG_E_UNSUPPORTED;
-  *fn = kernels(p->kid).*slot;
-  if (!*fn) return PCG_E_UNSUPPORTED;
-  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  if (v) {
+    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
+    if (kind != ClosedLoopKind::base && v->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;
+    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
+    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
+  }
+  // a squashed Gaussian's density carries the map's Jacobian: not these calls
+  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
+  if (!sigma) return PCG_E_NULL;
+  for (int i = 0; i < c.na; ++i)
+    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  std::memset(aa, 0, sizeof(*aa));
+  aa->P = (const PCG_CONSTANT PolicyDev*)q->dP;
+  aa->V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
+  aa->a_out = a_out; aa->ao_ss = ao_ss; aa->ao_cs = ao_cs;
+  aa->u_out = u_out; aa->uo_ss = uo_ss; aa->uo_cs = uo_cs;
+  aa->lp_out = lp_out; aa->lp_ss = lp_ss;
+  aa->v_out = v ? v_out : nullptr; aa->v_ss = v_ss;
+  for (int i = 0; i < c.na; ++i) aa->sigma[i] = sigma[i];
+  aa->c0 = pcg_actor_logp_const(sigma, c.na);
+  aa->record_next = record_next ? 1 : 0;
+  *late = (v && v->dtype != q->dtype) ? PCG_E_UNSUPPORTED : f32_on_jit(p, q);
   return PCG_OK;
 }
 
@@ -1914,12 +1955,14 @@ static bool feat_route_of_step(const pcg_plan* p, const pcg_buffers* io) {
   return feat_pick(p, k, &b, 0, lds_stages_on(p, k), false) >= 0;
 }
 
-// `cons` (the constrained entry points): the recorded rows and flags; the launch then carries a ConsArgs as its third argument
-template <class Fn, class HeadArgs>
-static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, Fn fn, const HeadArgs& head, const ClosedLoopRun& r,
-                              std::initializer_list<SeqRec> head_recs, int f32, int late_status, void* stream,
-                              const ConsRec* cons = nullptr, bool unc = false) {
+// `cons`: what ClosedLoopKind::cons adds (null for the other two) -- the launch then carries a ConsArgs as its third argument;
+// `late_status`: what the heads found and the base kind refuses only after every other check (f32_on_jit, actor_head)
+template <class HeadArgs>
+static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, const void* fn, ClosedLoopKind kind, const ConsRec* cons,
+                              const HeadArgs& head, std::initializer_list<SeqRec> head_recs, const ClosedLoopRun& r, int late_status,
+                              void* stream) {
   const DevConst& c = p->hc;
+  const bool unc = kind == ClosedLoopKind::unc;
   if (r.T < 1 || r.t0 < 0 || (int64_t)r.t0 + (int64_t)r.T > 0x7fffffffLL) return PCG_E_VALUE;
   if (io->B == 0) return PCG_OK;
   if (!io->x || !io->obs || !io->rew || !io->done) return PCG_E_NULL;
@@ -1929,7 +1972,7 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
   if (r.obs_seq && r.obs_cs < io->B) return PCG_E_DIM;
   for (const SeqRec& h : head_recs)
     if (h.seq && h.comp_stride < io->B) return PCG_E_DIM;
-  if (cons) {
+  if (kind == ClosedLoopKind::cons) {
     // the rows a rollout WRITES must not overlap: flag rows a full batch apart, constraint rows either step-major or
     // component-major (the reference's axis order) -- pcg_rollout_strided's rule for the observation rows
     const int64_t B = io->B, n = c.ncon;
@@ -1941,14 +1984,16 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
       if (!step_major && !comp_major) return PCG_E_DIM;
     }
   }
-  // what the float32 form adds, after every other check: networks of two dtypes in one call (late_status), and a plan with
-  // run-time compiled code, whose closed-loop module carries the fp64 kernels alone -- nothing compiled, nothing launched
+  // what the float32 form adds, after every other check: networks of two dtypes in one call, float32 on a plan with run-time
+  // compiled code -- nothing compiled, nothing launched
   if (late_status != PCG_OK) return late_status;
-  if (f32 && p->jit_fn[0]) return PCG_E_UNSUPPORTED;
   a.t_scalar = r.t0; a.seed = r.seed; a.T = r.T;
   a.d = nullptr;  // (the shared schedule: a closed-loop rollout has no per-step explicit disturbance values)
   a.obs_seq = r.obs_seq; a.rew_seq = r.rew_seq;
   a.o_ss = r.obs_ss; a.o_cs = r.obs_cs; a.r_ss = r.rew_ss;
+  HeadArgs h = head;
+  ConsArgs g;
+  void* argv[3] = {&a, &h, &g};  // (a kernel reads as many as it takes: the third is the constrained kernels' alone)
   if (p->jit_fn[0]) {  // the plan's closed-loop module, built at its first use -- which must not be inside a stream capture
     if (!__atomic_load_n(&p->jit_pol, __ATOMIC_ACQUIRE)) {
       hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1959,23 +2004,18 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, F
       if (cap != hipStreamCaptureStatusNone) return PCG_E_UNSUPPORTED;  // (loading a module is not a capturable operation)
       PCG_TRY(jit_prepare_closed_loop(p));
     }
-    HeadArgs h = head;
-    void* argv[2] = {&a, &h};
     return (int)hipModuleLaunchKernel(cov_jit(jit_head_fn(p, head)), grid_for(io->B), 1, 1, BLOCK, 1, 1, 0, (hipStream_t)stream,
                                       argv, nullptr);
   }
-  if constexpr (std::is_invocable_v<Fn, const StepArgs, const HeadArgs, const ConsArgs>) {
-    ConsArgs g;
+  if (kind == ClosedLoopKind::cons) {
     g.g_seq = cons->g_seq; g.g_ss = cons->g_ss; g.g_cs = cons->g_cs;
     g.viol_seq = cons->viol_seq; g.v_ss = cons->v_ss;
     // (env_pre's own pre-step check and store_out see no row storage: the kernel writes the rows it summed itself)
     g.g_last = a.g; g.g_pre = a.g_pre;
     a.g = nullptr; a.g_pre = nullptr;
     g.order_w = feat_route_of_step(p, io) ? 1 : 0;
-    hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head, g);
-  } else {
-    hipLaunchKernelGGL(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, head);
   }
+  (void)hipLaunchKernel(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), argv, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 }  // extern "C++"
@@ -1985,14 +2025,11 @@ int pcg_rollout_policy(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, 
                        int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
                        uint64_t seed, void* stream) {
   StepArgs a;
-  PolFn fn;
-  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_policy, &Kernels::roll_policy_f32, &a, &fn));
-  PolicyArgs pa;
-  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
-  pa.record_next = record_next_action ? 1 : 0;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::base, false, &a, &fn));
+  const PolicyArgs pa = policy_head(q, a_seq_out, a_step_stride, a_comp_stride, record_next_action);
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, q->dtype == PCG_POL_F32, PCG_OK, stream);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::base, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, f32_on_jit(p, q), stream);
 }
 
 int pcg_rollout_policy_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
@@ -2001,15 +2038,12 @@ int pcg_rollout_policy_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy
                             double* g_seq, int64_t g_step_stride, int64_t g_comp_stride, uint8_t* viol_seq,
                             int64_t viol_step_stride, uint64_t seed, void* stream) {
   StepArgs a;
-  PolConsFn fn;
-  PCG_TRY(closed_loop_open<PolConsFn>(p, io, q, &Kernels::roll_policy_cons, nullptr, &a, &fn, true));
-  PolicyArgs pa;
-  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
-  pa.record_next = record_next_action ? 1 : 0;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::cons, false, &a, &fn));
+  const PolicyArgs pa = policy_head(q, a_seq_out, a_step_stride, a_comp_stride, record_next_action);
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
-  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, 0, PCG_OK, stream, &rec);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::cons, &rec, pa, {{a_seq_out, a_comp_stride}}, run, f32_on_jit(p, q), stream);
 }
 
 int pcg_rollout_policy_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, int32_t t0, int32_t T, double* a_seq_out,
@@ -2017,14 +2051,11 @@ int pcg_rollout_policy_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy*
                            int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action,
                            uint64_t seed, void* stream) {
   StepArgs a;
-  PolFn fn;
-  PCG_TRY(closed_loop_open_unc<PolFn>(p, io, q, &Kernels::roll_policy_unc, &a, &fn));
-  PolicyArgs pa;
-  pa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
-  pa.record_next = record_next_action ? 1 : 0;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::unc, false, &a, &fn));
+  const PolicyArgs pa = policy_head(q, a_seq_out, a_step_stride, a_comp_stride, record_next_action);
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, pa, run, {{a_seq_out, a_comp_stride}}, 0, PCG_OK, stream, nullptr, true);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::unc, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, f32_on_jit(p, q), stream);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {
@@ -2055,35 +2086,15 @@ int pcg_rollout_actor(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, c
                       int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
                       int32_t record_next_action, uint64_t seed, void* stream) {
   StepArgs a;
-  ActFn fn;
-  PCG_TRY(closed_loop_open(p, io, q, &Kernels::roll_actor, &Kernels::roll_actor_f32, &a, &fn));
-  const DevConst& c = p->hc;
-  if (v) {
-    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
-    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
-    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
-  }
-  // a squashed Gaussian's density carries the map's Jacobian: not this call
-  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
-  if (!sigma) return PCG_E_NULL;
-  for (int i = 0; i < c.na; ++i)
-    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::base, true, &a, &fn));
   ActorArgs aa;
-  std::memset(&aa, 0, sizeof(aa));
-  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
-  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
-  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
-  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
-  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
-  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
-  aa.c0 = pcg_actor_logp_const(sigma, c.na);
-  aa.record_next = record_next_action ? 1 : 0;
+  int late;
+  PCG_TRY(actor_head(p, ClosedLoopKind::base, q, v, sigma, a_seq_out, a_step_stride, a_comp_stride, u_seq_out, u_step_stride, u_comp_stride,
+                     logp_out, logp_step_stride, value_out, value_step_stride, record_next_action, &aa, &late));
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  // (one kernel evaluates both networks: an actor and a critic of different dtypes are refused, after every other check)
-  const int mixed = (v && v->dtype != q->dtype) ? PCG_E_UNSUPPORTED : PCG_OK;
-  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, q->dtype == PCG_POL_F32,
-                            mixed, stream);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::base, nullptr, aa, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, run,
+                            late, stream);
 }
 
 int pcg_rollout_actor_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, const pcg_policy* v, const double* sigma,
@@ -2094,33 +2105,16 @@ int pcg_rollout_actor_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy*
                            int32_t record_next_action, double* g_seq, int64_t g_step_stride, int64_t g_comp_stride,
                            uint8_t* viol_seq, int64_t viol_step_stride, uint64_t seed, void* stream) {
   StepArgs a;
-  ActConsFn fn;
-  PCG_TRY(closed_loop_open<ActConsFn>(p, io, q, &Kernels::roll_actor_cons, nullptr, &a, &fn, true));
-  const DevConst& c = p->hc;
-  if (v) {
-    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
-    if (v->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;  // (the constrained kernels are built for fp64 networks)
-    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
-    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
-  }
-  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
-  if (!sigma) return PCG_E_NULL;
-  for (int i = 0; i < c.na; ++i)
-    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::cons, true, &a, &fn));
   ActorArgs aa;
-  std::memset(&aa, 0, sizeof(aa));
-  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
-  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
-  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
-  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
-  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
-  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
-  aa.c0 = pcg_actor_logp_const(sigma, c.na);
-  aa.record_next = record_next_action ? 1 : 0;
+  int late;
+  PCG_TRY(actor_head(p, ClosedLoopKind::cons, q, v, sigma, a_seq_out, a_step_stride, a_comp_stride, u_seq_out, u_step_stride, u_comp_stride,
+                     logp_out, logp_step_stride, value_out, value_step_stride, record_next_action, &aa, &late));
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
-  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, 0, PCG_OK, stream, &rec);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::cons, &rec, aa, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, run,
+                            late, stream);
 }
 
 int pcg_rollout_actor_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* q, const pcg_policy* v, const double* sigma,
@@ -2130,33 +2124,15 @@ int pcg_rollout_actor_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy* 
                           int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
                           int32_t record_next_action, uint64_t seed, void* stream) {
   StepArgs a;
-  ActFn fn;
-  PCG_TRY(closed_loop_open_unc<ActFn>(p, io, q, &Kernels::roll_actor_unc, &a, &fn));
-  const DevConst& c = p->hc;
-  if (v) {
-    if (v->magic != POLICY_MAGIC || v->device != p->device) return PCG_E_PLAN;
-    if (v->dtype == PCG_POL_F32) return PCG_E_UNSUPPORTED;  // (the kernels for per-env parameters are built for fp64 networks)
-    if (v->n_in != c.nobs || v->n_out != 1) return PCG_E_DIM;
-    if (v->out_map != PCG_POL_NONE) return PCG_E_VALUE;
-  }
-  if (q->out_map == PCG_POL_TANH) return PCG_E_UNSUPPORTED;
-  if (!sigma) return PCG_E_NULL;
-  for (int i = 0; i < c.na; ++i)
-    if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0)) return PCG_E_VALUE;
+  const void* fn;
+  PCG_TRY(closed_loop_open(p, io, q, ClosedLoopKind::unc, true, &a, &fn));
   ActorArgs aa;
-  std::memset(&aa, 0, sizeof(aa));
-  aa.P = (const PCG_CONSTANT PolicyDev*)q->dP;
-  aa.V = v ? (const PCG_CONSTANT PolicyDev*)v->dP : nullptr;
-  aa.a_out = a_seq_out; aa.ao_ss = a_step_stride; aa.ao_cs = a_comp_stride;
-  aa.u_out = u_seq_out; aa.uo_ss = u_step_stride; aa.uo_cs = u_comp_stride;
-  aa.lp_out = logp_out; aa.lp_ss = logp_step_stride;
-  aa.v_out = v ? value_out : nullptr; aa.v_ss = value_step_stride;
-  for (int i = 0; i < c.na; ++i) aa.sigma[i] = sigma[i];
-  aa.c0 = pcg_actor_logp_const(sigma, c.na);
-  aa.record_next = record_next_action ? 1 : 0;
+  int late;
+  PCG_TRY(actor_head(p, ClosedLoopKind::unc, q, v, sigma, a_seq_out, a_step_stride, a_comp_stride, u_seq_out, u_step_stride, u_comp_stride,
+                     logp_out, logp_step_stride, value_out, value_step_stride, record_next_action, &aa, &late));
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, aa, run, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, 0, PCG_OK, stream, nullptr,
-                            true);
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::unc, nullptr, aa, {{a_seq_out, a_comp_stride}, {u_seq_out, u_comp_stride}}, run,
+                            late, stream);
 }
 
 int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream) {

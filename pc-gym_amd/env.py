@@ -337,19 +337,8 @@ class VecEnv:
         plan with a reward expression compiles its closed-loop kernels at the first such call (``prepare_closed_loop``).
         The policy's dtype decides the kernel: a float32 policy is evaluated in float32 (every recorded output is a float32
         value; built-in plans only), the env arithmetic is fp64 either way."""
-        if self.per_env_t:
-            raise ValueError("rollout_policy() is lock-stepped only")
-        s, dev, B, T = self.spec, self.device, self.B, int(T)
-        R = T + (1 if record_next_action else 0)
-        a_seq, obs_seq, rew_seq = self._seq_buffers(
-            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
-        self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_policy(
-            self._plan, self._bufp, policy.handle(dev), self.t, T,
-            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_policy")
-        self.t += T
-        return a_seq, obs_seq, rew_seq
+        o = self._rollout_policy("rollout_policy", policy, T, collect_obs, collect_rew, collect_actions, record_next_action)
+        return o["a"], o["obs"], o["rew"]
 
     def rollout_actor(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
                       collect_logp=True, collect_values=True, record_next_action=False):
@@ -362,31 +351,61 @@ class VecEnv:
         t + T, not applied): its value is the bootstrap value.  Plans / networks the kernel does not take raise PcgError.
         Float32 networks (actor and critic of one dtype) are evaluated in float32: ``mu`` and the value are widened float32
         results, the sample, the map and the log-probability are fp64 as for float64 networks."""
+        return self._rollout_actor("rollout_actor", ac, T, collect_obs, collect_rew, collect_actions, collect_samples, collect_logp,
+                                   collect_values, record_next_action)
+
+    def _cons_record(self, T, cons, out):
+        """what a ``_cons`` entry point takes beside its base form's arguments; adds "g" (T, ncon, B) | None and "viol" (T, B) bool
+        (a view of the kernel's bytes) | None to ``out``.  ``cons``: (collect_g, collect_viol), or None for the other forms"""
+        if cons is None:
+            return ()
+        torch = _torch()
+        if not self.spec.ncon:
+            raise ValueError("this plan has no constraint rows: use rollout_policy() / rollout_actor()")
+        g, = self._seq_buffers(((T, self.spec.ncon, self.B), cons[0]))
+        viol = torch.empty((T, self.B), dtype=torch.uint8, device=self.device) if cons[1] else None
+        out.update(g=g, viol=viol.view(torch.bool) if viol is not None else None)
+        return _ptr(g), self.spec.ncon * self.B, self.B, _ptr(viol), self.B
+
+    def _rollout_policy(self, name, policy, T, collect_obs, collect_rew, collect_actions, record_next_action, cons=None):
+        """the three ``rollout_policy*`` methods: buffers, the call of ``pcg_<name>``, the step counter -> dict of what was recorded"""
         if self.per_env_t:
-            raise ValueError("rollout_actor() is lock-stepped only")
+            raise ValueError(f"{name}() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, obs_seq, rew_seq = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        out = {"a": a_seq, "obs": obs_seq, "rew": rew_seq}
+        rows = self._cons_record(T, cons, out)
+        self._buf.d = None
+        _lib.check(getattr(self._lib, "pcg_" + name)(
+            self._plan, self._bufp, policy.handle(dev), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), *rows, self._episode_seed(), self._stream()), "pcg_" + name)
+        self.t += T
+        return out
+
+    def _rollout_actor(self, name, ac, T, collect_obs, collect_rew, collect_actions, collect_samples, collect_logp, collect_values,
+                       record_next_action, cons=None):
+        """the three ``rollout_actor*`` methods, as ``_rollout_policy``"""
+        if self.per_env_t:
+            raise ValueError(f"{name}() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)
         R = T + (1 if record_next_action else 0)
         a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
             ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
             ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
+        out = {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
+        rows = self._cons_record(T, cons, out)
         self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_actor(
+        _lib.check(getattr(self._lib, "pcg_" + name)(
             self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
             ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
             _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
             _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_actor")
+            int(bool(record_next_action)), *rows, self._episode_seed(), self._stream()), "pcg_" + name)
         self.t += T
-        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
-
-    def _cons_buffers(self, T, collect_g, collect_viol):
-        """(g (T, ncon, B) | None, viol (T, B) uint8 | None) of a fused closed-loop rollout on a plan with constraint rows"""
-        torch = _torch()
-        if not self.spec.ncon:
-            raise ValueError("this plan has no constraint rows: use rollout_policy() / rollout_actor()")
-        g, = self._seq_buffers(((T, self.spec.ncon, self.B), collect_g))
-        viol = torch.empty((T, self.B), dtype=torch.uint8, device=self.device) if collect_viol else None
-        return g, viol
+        return out
 
     def rollout_policy_cons(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
                             record_next_action=False, collect_g=True, collect_viol=True):
@@ -397,47 +416,16 @@ class VecEnv:
         t = 0 -- what the step() loop leaves, bit for bit.  An env whose ``done`` is set mid-episode (``done_on_cons_vio``) keeps
         stepping, as in that loop.  Plans the kernel does not take (no rows, constraint expressions, user models, per-env
         parameters, integrators other than rk4 / cv8) and float32 policies raise PcgError."""
-        if self.per_env_t:
-            raise ValueError("rollout_policy_cons() is lock-stepped only")
-        s, dev, B, T = self.spec, self.device, self.B, int(T)
-        R = T + (1 if record_next_action else 0)
-        a_seq, obs_seq, rew_seq = self._seq_buffers(
-            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
-        g_seq, viol = self._cons_buffers(T, collect_g, collect_viol)
-        self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_policy_cons(
-            self._plan, self._bufp, policy.handle(dev), self.t, T,
-            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), _ptr(g_seq), s.ncon * B, B, _ptr(viol), B,
-            self._episode_seed(), self._stream()), "pcg_rollout_policy_cons")
-        self.t += T
-        return {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "g": g_seq,
-                "viol": viol.view(_torch().bool) if viol is not None else None}
+        return self._rollout_policy("rollout_policy_cons", policy, T, collect_obs, collect_rew, collect_actions, record_next_action,
+                                    cons=(collect_g, collect_viol))
 
     def rollout_actor_cons(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
                            collect_logp=True, collect_values=True, record_next_action=False, collect_g=True,
                            collect_viol=True):
         """``rollout_actor`` on a plan WITH constraint rows (``pcg_rollout_actor_cons``): its dict plus "g" (T, ncon, B) and
         "viol" (T, B) bool, as ``rollout_policy_cons`` records them; float64 networks only."""
-        if self.per_env_t:
-            raise ValueError("rollout_actor_cons() is lock-stepped only")
-        s, dev, B, T = self.spec, self.device, self.B, int(T)
-        R = T + (1 if record_next_action else 0)
-        a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
-            ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
-            ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
-        g_seq, viol = self._cons_buffers(T, collect_g, collect_viol)
-        self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_actor_cons(
-            self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
-            ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
-            _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
-            _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), _ptr(g_seq), s.ncon * B, B, _ptr(viol), B,
-            self._episode_seed(), self._stream()), "pcg_rollout_actor_cons")
-        self.t += T
-        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq, "g": g_seq,
-                "viol": viol.view(_torch().bool) if viol is not None else None}
+        return self._rollout_actor("rollout_actor_cons", ac, T, collect_obs, collect_rew, collect_actions, collect_samples, collect_logp,
+                                   collect_values, record_next_action, cons=(collect_g, collect_viol))
 
     def rollout_policy_unc(self, policy, T, collect_obs=False, collect_rew=True, collect_actions=True,
                            record_next_action=False):
@@ -446,40 +434,15 @@ class VecEnv:
         last reset sampled -- is read and left as it is.
         Plans the kernel does not take (no per-env parameters, constraint rows, integrators other than rk4) and float32
         policies raise PcgError."""
-        if self.per_env_t:
-            raise ValueError("rollout_policy_unc() is lock-stepped only")
-        s, dev, B, T = self.spec, self.device, self.B, int(T)
-        R = T + (1 if record_next_action else 0)
-        a_seq, obs_seq, rew_seq = self._seq_buffers(
-            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
-        self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_policy_unc(
-            self._plan, self._bufp, policy.handle(dev), self.t, T,
-            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_policy_unc")
-        self.t += T
-        return a_seq, obs_seq, rew_seq
+        o = self._rollout_policy("rollout_policy_unc", policy, T, collect_obs, collect_rew, collect_actions, record_next_action)
+        return o["a"], o["obs"], o["rew"]
 
     def rollout_actor_unc(self, ac, T, collect_obs=False, collect_rew=True, collect_actions=True, collect_samples=True,
                           collect_logp=True, collect_values=True, record_next_action=False):
         """``rollout_actor`` on a plan WITH per-env parameters (``pcg_rollout_actor_unc``): its dict, the observation rows with
         the parameter slots, as ``rollout_policy_unc`` records them; float64 networks only."""
-        if self.per_env_t:
-            raise ValueError("rollout_actor_unc() is lock-stepped only")
-        s, dev, B, T = self.spec, self.device, self.B, int(T)
-        R = T + (1 if record_next_action else 0)
-        a_seq, u_seq, lp, val, obs_seq, rew_seq = self._seq_buffers(
-            ((R, s.na, B), collect_actions), ((R, s.na, B), collect_samples), ((R, B), collect_logp),
-            ((R, B), collect_values and ac.critic is not None), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew))
-        self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_actor_unc(
-            self._plan, self._bufp, ac.actor.handle(dev), ac.critic.handle(dev) if ac.critic is not None else None,
-            ac.sigma.ctypes.data_as(C.POINTER(C.c_double)), self.t, T,
-            _ptr(a_seq), s.na * B, B, _ptr(u_seq), s.na * B, B, _ptr(lp), B, _ptr(val), B,
-            _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), self._episode_seed(), self._stream()), "pcg_rollout_actor_unc")
-        self.t += T
-        return {"a": a_seq, "u": u_seq, "logp": lp, "val": val, "obs": obs_seq, "rew": rew_seq}
+        return self._rollout_actor("rollout_actor_unc", ac, T, collect_obs, collect_rew, collect_actions, collect_samples, collect_logp,
+                                   collect_values, record_next_action)
 
     def policy_noise(self, t=None, out=None):
         """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the

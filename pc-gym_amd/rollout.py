@@ -132,47 +132,34 @@ def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
         env.t += N - 1
         u = a if a_hm is None else _denorm_(a.clone(), a_hm, 1)  # never scale the caller's tensor in place
         return {"r": r, "x": _denorm_(x, o_hm, 0), "u": u.permute(1, 0, 2)}
+    # which fused closed-loop entry point takes this plan and policy, if any: pcg_rollout_policy<kind>
+    kind = None
     if policy is not None and fused_policy_ok(s, policy):
+        kind = ""
+    elif policy is not None and fused_cons_ok(s, policy):
+        kind = "_cons"
+    elif fused_unc:  # on request: the reset above sampled the parameters; the observation rows carry their slots, as the open loop's do
+        kind = "_unc"
+    if kind is not None:
         # closed loop in one launch: the kernel evaluates the policy between two steps and writes observations, policy
-        # outputs (column N-1: the action proposed for the final observation) and rewards in the reference's axis order
+        # outputs (column N-1: the action proposed for the final observation) and rewards in the reference's axis order;
+        # on a plan with constraint rows also every step's rows into g[:, 1:] (g[:, 0]: the first step's pre-step check,
+        # pcgym.py:414-420)
         x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
         u = torch.empty((s.na, N, B), dtype=f64, device=dev)
         x[:, 0] = env.obs_soa
+        rows = (g[:, 1:].data_ptr(), B, N * B, None, 0) if kind == "_cons" else ()
         env._buf.d = None
-        rc = env._lib.pcg_rollout_policy(
+        rc = getattr(env._lib, "pcg_rollout_policy" + kind)(
             env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
-            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, env._episode_seed(), env._stream())
-        _lib.check(rc, "pcg_rollout_policy")
+            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, *rows, env._episode_seed(), env._stream())
+        _lib.check(rc, "pcg_rollout_policy" + kind)
         env.t += N - 1
-        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
-    if policy is not None and fused_cons_ok(s, policy):
-        # the same on a plan with constraint rows (pcg_rollout_policy_cons): the kernel also writes every step's rows into
-        # g[:, 1:] in the reference's axis order; g[:, 0] is the pre-step check of the first step (pcgym.py:414-420)
-        x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
-        u = torch.empty((s.na, N, B), dtype=f64, device=dev)
-        x[:, 0] = env.obs_soa
-        env._buf.d = None
-        rc = env._lib.pcg_rollout_policy_cons(
-            env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
-            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, g[:, 1:].data_ptr(), B, N * B, None, 0,
-            env._episode_seed(), env._stream())
-        _lib.check(rc, "pcg_rollout_policy_cons")
-        env.t += N - 1
-        g[:, 0, 0] = env.g_pre
-        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0), "g": g}
-    if fused_unc:
-        # the same on a plan with per-env parameters (pcg_rollout_policy_unc), on request: the reset above sampled them; the
-        # observation rows carry the parameter slots, as those of the open-loop collector do
-        x = torch.empty((s.nobs, N, B), dtype=f64, device=dev)
-        u = torch.empty((s.na, N, B), dtype=f64, device=dev)
-        x[:, 0] = env.obs_soa
-        env._buf.d = None
-        rc = env._lib.pcg_rollout_policy_unc(
-            env._plan, env._bufp, policy.handle(dev), 0, N - 1, u.data_ptr(), B, N * B,
-            x[:, 1:].data_ptr(), B, N * B, r[:, 1:].data_ptr(), B, 1, env._episode_seed(), env._stream())
-        _lib.check(rc, "pcg_rollout_policy_unc")
-        env.t += N - 1
-        return {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
+        out = {"r": r, "x": _denorm_(x, o_hm, 0), "u": _denorm_(u, a_hm, 0)}
+        if kind == "_cons":
+            g[:, 0, 0] = env.g_pre
+            out["g"] = g
+        return out
     # per-step path: step-major storage, the env's kernels write into it
     xs = torch.empty((N, s.nobs, B), dtype=f64, device=dev)
     us = torch.empty((N, s.na, B), dtype=f64, device=dev)
@@ -279,30 +266,21 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
     if record_cons:
         cons = {"g": torch.empty((T, s.ncon, B), dtype=f64, device=dev), "g_pre": None,
                 "viol": torch.empty((T, B), dtype=torch.uint8, device=dev)}
-    if record_cons and ok and fused is not False:
-        u = torch.empty((N, s.na, B), dtype=f64, device=dev)
-        env._buf.d = None
-        rc = env._lib.pcg_rollout_actor_cons(
-            env._plan, env._bufp, ac.actor.handle(dev), ac.critic.handle(dev), ac.sigma.ctypes.data_as(C.POINTER(C.c_double)),
-            0, T, None, 0, 0, u.data_ptr(), s.na * B, B, logp.data_ptr(), B, val.data_ptr(), B,
-            obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, cons["g"].data_ptr(), s.ncon * B, B,
-            cons["viol"].data_ptr(), B, env._episode_seed(), env._stream())
-        _lib.check(rc, "pcg_rollout_actor_cons")
-        env.t += T
-        act = u[:T]
-        cons["g_pre"] = env.g_pre.clone()
-    elif ok and fused is not False:
+    if ok and fused is not False:
         # (row N-1 of the samples is drawn and dropped: only its value, the bootstrap value, is kept)
         u = torch.empty((N, s.na, B), dtype=f64, device=dev)
+        name = "pcg_rollout_actor" + ("_cons" if record_cons else "_unc" if unc else "")
+        rows = (cons["g"].data_ptr(), s.ncon * B, B, cons["viol"].data_ptr(), B) if record_cons else ()
         env._buf.d = None
-        name = "pcg_rollout_actor_unc" if unc else "pcg_rollout_actor"
         rc = getattr(env._lib, name)(
             env._plan, env._bufp, ac.actor.handle(dev), ac.critic.handle(dev), ac.sigma.ctypes.data_as(C.POINTER(C.c_double)),
             0, T, None, 0, 0, u.data_ptr(), s.na * B, B, logp.data_ptr(), B, val.data_ptr(), B,
-            obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, env._episode_seed(), env._stream())
+            obs[1:].data_ptr(), s.nobs * B, B, rew.data_ptr(), B, 1, *rows, env._episode_seed(), env._stream())
         _lib.check(rc, name)
         env.t += T
         act = u[:T]
+        if record_cons:
+            cons["g_pre"] = env.g_pre.clone()
     else:
         z = torch.empty((s.na, B), dtype=f64, device=dev)
         with _recording(env):

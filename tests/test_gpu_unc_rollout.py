@@ -390,7 +390,7 @@ def test_refusals_launch_nothing():
     # ---- the plans: PCG_E_UNSUPPORTED, in the header's order ----
     # (the run-time compiled plan, the affine registry model and `plain` all have nunc == 0 and are refused by that clause:
     # pcg_plan_create itself refuses nunc > 0 on run-time compiled and on affine / user models, so no plan can reach
-    # closed_loop_open_unc's own checks of those two through the public interface, and this test does not cover them alone)
+    # closed_loop_open's own `unc` checks of those two through the public interface, and this test does not cover them alone)
     unc = _params("cstr")
     plain = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
     plain.update(integrator="rk4")
