@@ -122,7 +122,8 @@ def constrained(actor_net, B):
     """the same envs with constraint rows (a temperature band, -1000 penalty while outside): the fused calls record every
     step's rows and violation flags -- `g` of collect_rollouts in the reference's axis order, `g` / `g_pre` / `viol` of
     collect_onpolicy(record_cons=True): a cost signal or a mask for a constrained trainer.  An env that violates keeps
-    stepping; mask what follows from `viol`."""
+    stepping; with terminate_on_violation=True the advantage recursion is cut at the violating step (one launch, pcg_gae,
+    with `viol` as its termination mask) and `alive` marks the steps up to and including it: the mask for the loss."""
     # (reference_compat=False: the rows read the physical state; the reference hands its constraint callable a state it has
     # "de-normalised" a second time when normalise_o is set -- quirk Q3 -- and a band in kelvin means nothing there)
     p = dict(copy.deepcopy(env_params), r_penalty=True, done_on_cons_vio=False, reference_compat=False,
@@ -143,10 +144,12 @@ def constrained(actor_net, B):
     ac = GaussianActorCritic.from_torch(actor_net, torch.full((1,), -1.0, dtype=torch.float64), critic_net, out_map="clip",
                                         out_low=-1.0, out_high=1.0)
     env = make_vec_env(p, n_envs=B, seed=0)
-    d = collect_onpolicy(env, ac, record_cons=True)
+    d = collect_onpolicy(env, ac, record_cons=True, terminate_on_violation=True)
     first = torch.where(d["viol"].any(dim=0), d["viol"].double().argmax(dim=0), d["viol"].shape[0])
     print(f"constrained actor-critic: g {tuple(d['g'].shape)} g_pre {tuple(d['g_pre'].shape)} viol {tuple(d['viol'].shape)}  "
           f"envs that violate at some step {d['viol'].any(dim=0).double().mean().item():.3f}, first at step {first.double().mean().item():.1f} on average")
+    print(f"terminate_on_violation: alive {tuple(d['alive'].shape)}  steps alive {d['alive'].double().mean().item():.3f}  "
+          f"mean |adv| over the alive steps {d['adv'][d['alive']].abs().mean().item():.3f}")
     env.close(), ac.close(), policy.close()
 
 

@@ -680,6 +680,35 @@ PCG_API double pcg_actor_logp_const(const double* sigma, int32_t na);
  * for a caller that samples outside the fused call (one pcg_step per step).  na and the env offset are the plan's. */
 PCG_API int pcg_policy_noise(pcg_plan* plan, int64_t B, int32_t t, uint64_t seed, double* z_out, void* stream);
 
+/* Generalised advantage estimation (Schulman et al. 2016) over one recorded episode, all B envs in ONE launch (additive
+ * under ABI 16; kernel: csrc/pcg_gae.hpp): what an on-policy trainer forms from the rows pcg_rollout_actor and
+ * pcg_rollout_actor_cons record.  The interface is that of stable-baselines3's
+ * RolloutBuffer.compute_returns_and_advantage: `term` is its episode-start mask seen from the step before
+ * (next_non_terminal = !term[t]), bootstrap_last = 0 its `dones` of the last step, val[T] its `last_values`.
+ *   rew [T][B], val [T+1][B] (val[T]: the value of the observation after the last step), term [T][B] bytes or NULL
+ *   (non-zero: the episode ended WITH step t -- e.g. viol_seq of pcg_rollout_actor_cons), adv [T][B], ret [T][B] or NULL;
+ *   element (t, e) of each array is at t * its step stride + e.  All device memory; outputs must not overlap inputs.
+ * Per env, backwards in time, with gl = gamma * lam rounded once on the host:
+ *     carry = 0
+ *     for t = T-1 .. 0:
+ *         cut   = (term && term[t] != 0) || (t == T-1 && !bootstrap_last)
+ *         nxt   = cut ? 0.0 : val[t+1];   c = cut ? 0.0 : carry
+ *         delta = (rew[t] + gamma * nxt) - val[t]        three operations, each rounded
+ *         carry = delta + gl * c                          two operations, each rounded
+ *         adv[t] = carry;   ret[t] = carry + val[t]
+ * No operation is contracted into a fused multiply-add and the products with zero are carried out, so the result is a
+ * fixed rounding sequence: the same bits for every batch size, stride, alignment and launch shape (two envs per lane with
+ * 16-byte accesses where B is even and all rows are 16-byte aligned, one env per lane otherwise), and the bits of the
+ * same sequence written in any IEEE-754 double arithmetic (NaN payloads aside).  A NaN or infinity stays in its own env.
+ * Status, nothing launched on any of them, in this order: PCG_E_NULL for rew, val or adv == NULL; PCG_E_DIM for B < 1 or
+ * T < 1; PCG_E_DIM for val_step_stride < B, and while T > 1 for any other step stride < B (term's and ret's only when
+ * they are given); PCG_E_VALUE for a gamma or lam that is not finite.
+ * There is no plan: the launch goes to `stream` on the caller's current device.  Reads and writes only its arguments; no
+ * allocation, no memset: safe under stream capture.  Not here: float32 arrays, advantage normalisation, per-env counters. */
+PCG_API int pcg_gae(int64_t B, int32_t T, const double* rew, int64_t rew_step_stride, const double* val, int64_t val_step_stride,
+                    const uint8_t* term, int64_t term_step_stride, double gamma, double lam, int32_t bootstrap_last,
+                    double* adv, int64_t adv_step_stride, double* ret, int64_t ret_step_stride, void* stream);
+
 /* pcg_step followed, in the same launch, by the reset of every env that finished in it (gymnasium "same-step"
  * auto-reset: rew / done / viol are those of the finished step; x, obs, t, a_save and the per-env parameters are
  * those of the new episode, drawn with `reset_seed`).  Equivalent to pcg_step + pcg_reset(mask = io->done,

@@ -217,6 +217,7 @@ EXPORTS = [
     "pcg_rollout_actor_unc",
     "pcg_actor_logp_const",
     "pcg_policy_noise",
+    "pcg_gae",
     "pcg_step_autoreset",
     "pcg_graph_create",
     "pcg_graph_launch",
@@ -304,6 +305,9 @@ def declare(lib):
     lib.pcg_actor_logp_const.argtypes = [_pd, C.c_int32]
     lib.pcg_policy_noise.restype = C.c_int
     lib.pcg_policy_noise.argtypes = [vp, C.c_int64, C.c_int32, C.c_uint64, vp, vp]
+    lib.pcg_gae.restype = C.c_int
+    lib.pcg_gae.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_int32,
+                            vp, C.c_int64, vp, C.c_int64, vp]
     lib.pcg_step_autoreset.restype = C.c_int
     lib.pcg_step_autoreset.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_uint64, C.c_uint64, vp]
     lib.pcg_graph_create.restype = C.c_int

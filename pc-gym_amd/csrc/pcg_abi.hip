@@ -3,6 +3,7 @@
 // live in pcg_kernels.hpp; each model's instantiations are compiled in a pcg_inst_*.hip unit.
 #include "pcg_kernels.hpp"
 #include "pcg_step_feat.hpp"
+#include "pcg_gae.hpp"
 
 #include <hip/hiprtc.h>
 #include <dirent.h>
@@ -2143,6 +2144,48 @@ int pcg_policy_noise(pcg_plan* p, int64_t B, int32_t t, uint64_t seed, double* z
   if (!z_out) return PCG_E_NULL;
   hipLaunchKernelGGL(cov(policy_noise_kernel), dim3(grid_for(B)), dim3(BLOCK), 0, (hipStream_t)stream, B, (int32_t)p->hc.na, seed,
                      p->env_offset, (uint32_t)t, z_out);
+  return (int)hipGetLastError();
+}
+
+// two envs per lane with 16-byte accesses (2-byte for the flags): the rule of the lean kernels' tile I/O (step_lean, rollout_lean) --
+// an even batch and every row 16-byte aligned, which here, with caller-given strides, asks for even strides as well
+static bool gae_vec2_ok(int64_t B, int32_t T, const double* rew, int64_t rew_ss, const double* val, int64_t val_ss, const uint8_t* term,
+                        int64_t term_ss, const double* adv, int64_t adv_ss, const double* ret, int64_t ret_ss) {
+  const bool rows = T > 1;  // (a single row has no stride to speak of; val has T + 1 rows)
+  return B % 2 == 0 && al16(rew) && al16(val) && al16(adv) && al16(ret) && al2(term) && val_ss % 2 == 0 &&
+         (!rows || (rew_ss % 2 == 0 && adv_ss % 2 == 0 && (!ret || ret_ss % 2 == 0) && (!term || term_ss % 2 == 0)));
+}
+
+int pcg_gae(int64_t B, int32_t T, const double* rew, int64_t rew_step_stride, const double* val, int64_t val_step_stride,
+            const uint8_t* term, int64_t term_step_stride, double gamma, double lam, int32_t bootstrap_last, double* adv,
+            int64_t adv_step_stride, double* ret, int64_t ret_step_stride, void* stream) {
+  if (!rew || !val || !adv) return PCG_E_NULL;
+  if (B < 1 || T < 1) return PCG_E_DIM;
+  if (val_step_stride < B) return PCG_E_DIM;
+  if (T > 1 && (rew_step_stride < B || adv_step_stride < B || (term && term_step_stride < B) || (ret && ret_step_stride < B)))
+    return PCG_E_DIM;
+  if (!std::isfinite(gamma) || !std::isfinite(lam)) return PCG_E_VALUE;
+  GaeArgs a;
+  a.B = B;
+  a.T = T;
+  a.bootstrap_last = bootstrap_last != 0;
+  a.vec2 = gae_vec2_ok(B, T, rew, rew_step_stride, val, val_step_stride, term, term_step_stride, adv, adv_step_stride, ret, ret_step_stride);
+  a.gamma = gamma;
+  a.gl = gamma * lam;  // rounded once, here: the torch loop's `gamma * lam * last` is (gamma * lam) * last
+  a.rew = rew;
+  a.val = val;
+  a.term = term;
+  a.adv = adv;
+  a.ret = ret;
+  a.rew_ss = rew_step_stride;
+  a.val_ss = val_step_stride;
+  a.term_ss = term_step_stride;
+  a.adv_ss = adv_step_stride;
+  a.ret_ss = ret_step_stride;
+  const int64_t lanes = a.vec2 ? B / 2 : B;
+  const int64_t grid = (lanes + GAE_BLOCK - 1) / GAE_BLOCK;
+  if (grid > INT32_MAX) return PCG_E_DIM;
+  hipLaunchKernelGGL(cov(gae_kernel), dim3((unsigned)grid), dim3(GAE_BLOCK), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 

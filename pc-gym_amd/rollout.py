@@ -186,29 +186,91 @@ def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
     return out
 
 
-def gae(rew, val, gamma=0.99, lam=0.95, bootstrap_last=False):
+def _gae_fusable(rew, val, term):
+    """why these tensors cannot go through ``pcg_gae`` (a string), or None: float64, on one GPU, 2-D, unit stride along B --
+    row-sliced or padded views qualify through their row strides"""
+    torch = _torch()
+    if not rew.is_cuda:
+        return "the tensors are not on a GPU"
+    if rew.dim() != 2:
+        return f"rew has {rew.dim()} dimensions, not 2"
+    T, B = rew.shape
+    if T < 1 or B < 1:
+        return "an empty array"
+    for name, t, want in (("rew", rew, torch.float64), ("val", val, torch.float64), ("term", term, (torch.bool, torch.uint8))):
+        if t is None:
+            continue
+        if t.dtype != want and not (isinstance(want, tuple) and t.dtype in want):
+            return f"{name} is {t.dtype}"
+        if t.device != rew.device:
+            return f"{name} is on {t.device}, rew on {rew.device}"
+        if B > 1 and t.stride(1) != 1:
+            return f"{name} has stride {t.stride(1)} along the env axis"
+        if t.shape[0] > 1 and t.stride(0) < B:
+            return f"{name} has row stride {t.stride(0)} < B = {B}"
+    return None
+
+
+def gae(rew, val, gamma=0.99, lam=0.95, bootstrap_last=False, term=None, fused=None):
     """Generalised advantage estimation over one episode for all envs at once (Schulman et al. 2016; stable-baselines3's
     ``RolloutBuffer.compute_returns_and_advantage``): rew (T, B), val (T + 1, B) -> (adv (T, B), ret (T, B)).
 
         delta_t = rew_t + gamma val_{t+1} - val_t;   adv_t = delta_t + gamma lam adv_{t+1};   ret_t = adv_t + val_t
 
     ``val[T]`` is the value of the observation after the last step.  ``bootstrap_last=False`` treats the episode's end as
-    terminal (val[T] does not enter); ``True`` bootstraps from it (a time-limit truncation)."""
+    terminal (val[T] does not enter); ``True`` bootstraps from it (a time-limit truncation).
+
+    ``term`` (T, B), bool or uint8: true where the episode of that env ENDED with step t (stable-baselines3's
+    ``next_non_terminal`` is its negation).  There the recursion is cut: neither ``val[t+1]`` nor ``adv[t+1]`` enter step t.
+
+    ``fused``: None takes ONE kernel launch (``pcg_gae``) when the tensors are float64, on a GPU, 2-D and have unit stride
+    along B, and the loop of element-wise torch calls below otherwise (CPU tensors, other dtypes, more dimensions); False
+    always takes the loop; True raises ValueError unless the kernel can take the tensors.  The two return the same bits:
+    the kernel performs the loop's operations in the loop's order, each rounded on its own."""
     torch = _torch()
     T = rew.shape[0]
     if val.shape[0] != T + 1 or val.shape[1:] != rew.shape[1:]:
         raise ValueError(f"gae: rew {tuple(rew.shape)} needs val of shape ({T + 1}, ...), not {tuple(val.shape)}")
+    if term is not None:
+        if term.shape != rew.shape:
+            raise ValueError(f"gae: term must have rew's shape {tuple(rew.shape)}, not {tuple(term.shape)}")
+        if term.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"gae: term must be bool or uint8, not {term.dtype}")
+    why = None if fused is False else _gae_fusable(rew, val, term)
+    if fused and why is not None:
+        raise ValueError(f"gae(fused=True): {why}")
+    if fused is not False and why is None:
+        B = rew.shape[1]
+        adv = torch.empty((T, B), dtype=rew.dtype, device=rew.device)
+        ret = torch.empty((T, B), dtype=rew.dtype, device=rew.device)
+        with torch.cuda.device(rew.device):
+            rc = _lib.load().pcg_gae(
+                B, T, rew.data_ptr(), rew.stride(0), val.data_ptr(), val.stride(0),
+                term.data_ptr() if term is not None else None, term.stride(0) if term is not None else 0,
+                float(gamma), float(lam), int(bool(bootstrap_last)), adv.data_ptr(), B, ret.data_ptr(), B,
+                torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pcg_gae")
+        return adv, ret
     adv = torch.empty_like(rew)
     last = torch.zeros_like(rew[0])
+    zero = torch.zeros_like(rew[0])
     for t in range(T - 1, -1, -1):
-        nxt = val[t + 1] if (t < T - 1 or bootstrap_last) else torch.zeros_like(val[t])
+        end = t == T - 1 and not bootstrap_last
+        if term is None or end:
+            nxt = zero if end else val[t + 1]
+            c = zero if end else last
+        else:
+            cut = term[t] != 0
+            nxt = torch.where(cut, zero, val[t + 1])
+            c = torch.where(cut, zero, last)
         delta = rew[t] + gamma * nxt - val[t]
-        last = delta + gamma * lam * last
+        last = delta + gamma * lam * c
         adv[t] = last
     return adv, adv + val[:T]
 
 
-def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None, record_cons=False, fused_unc=False):
+def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=None, record_cons=False, fused_unc=False,
+                     terminate_on_violation=False):
     """One episode (N - 1 steps) of all B envs under the stochastic actor-critic ``ac`` (a
     :class:`~pcgym_amd.policy.GaussianActorCritic` with a critic): what an on-policy trainer such as PPO collects.
 
@@ -218,7 +280,7 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
         logp (N-1, B)      log N(u; mu, sigma^2)
         val  (N, B)        critic values of obs; row N-1 is the bootstrap value
         rew  (N-1, B)
-        adv, ret (N-1, B)  from :func:`gae`
+        adv, ret (N-1, B)  from :func:`gae` (one more launch, ``pcg_gae``, on either route)
 
     Route: ONE launch (``pcg_rollout_actor``) when the plan and the networks qualify (``fused_actor_ok``: RK4 / CV8, no
     constraint rows, no per-env parameters, no tanh map; user models and reward expressions included); otherwise -- or with ``fused=False`` -- one
@@ -235,7 +297,14 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
         viol  (N-1, B)        bool, any row > 0
     on both routes: ONE launch (``pcg_rollout_actor_cons``) when ``fused_actor_cons_ok`` (a built-in RK4 / CV8 plan with
     affine rows, float64 networks), the per-step loop otherwise or with ``fused=False``; ``fused=True`` then raises only
-    when ``fused_actor_cons_ok`` is false.  An env whose ``done`` is set mid-episode keeps stepping on both routes."""
+    when ``fused_actor_cons_ok`` is false.  An env whose ``done`` is set mid-episode keeps stepping on both routes.
+
+    ``terminate_on_violation=True`` (needs ``record_cons=True``, ValueError otherwise) treats a violation as the end of that
+    env's episode in the estimator, as every on-policy trainer treats a terminal step: ``viol`` is passed to :func:`gae` as
+    ``term``, so ``adv`` / ``ret`` of a violating step see neither the value nor the advantage of what follows.  The env
+    still steps on; what follows is recorded and marked by one more entry,
+        alive (N-1, B)  bool, no EARLIER step of that env violated (the violating step itself is alive)
+    the mask for the trainer's loss.  The default returns today's dict with today's values."""
     torch = _torch()
     s = env.spec
     B, N, dev, f64 = env.B, s.N, env.device, torch.float64
@@ -255,6 +324,8 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
     obs[0] = env.obs_soa
     if record_cons and not s.ncon:
         raise ValueError("record_cons: this plan has no constraint rows")
+    if terminate_on_violation and not record_cons:
+        raise ValueError("terminate_on_violation needs record_cons=True: the violation flags are what cuts the recursion")
     # a plan with per-env parameters: pcg_rollout_actor_unc, on request only (the default route of such a plan stays the step loop)
     unc = bool(fused_unc)
     if unc and (record_cons or fused is False or not fused_actor_unc_ok(s, ac)):
@@ -299,11 +370,15 @@ def collect_onpolicy(env, ac, gamma=0.99, lam=0.95, bootstrap_last=False, fused=
                     cons["g"][i] = env.g
                     cons["viol"][i] = env.viol
             val[T] = ac.value(o)
-    adv, ret = gae(rew, val, gamma, lam, bootstrap_last)
+    adv, ret = gae(rew, val, gamma, lam, bootstrap_last, term=cons["viol"] if terminate_on_violation else None)
     out = {"obs": obs, "act": act, "logp": logp[:T], "val": val, "rew": rew, "adv": adv, "ret": ret}
     if record_cons:
         cons["viol"] = cons["viol"].view(torch.bool)
         out.update(cons)
+    if terminate_on_violation:  # exclusive cumulative-or over the steps
+        alive = torch.ones((T, B), dtype=torch.bool, device=dev)
+        alive[1:] = torch.cumsum(cons["viol"][:-1], 0) == 0
+        out["alive"] = alive
     return out
 
 
