@@ -709,6 +709,53 @@ PCG_API int pcg_gae(int64_t B, int32_t T, const double* rew, int64_t rew_step_st
                     const uint8_t* term, int64_t term_step_stride, double gamma, double lam, int32_t bootstrap_last,
                     double* adv, int64_t adv_step_stride, double* ret, int64_t ret_step_stride, void* stream);
 
+/* A POPULATION of policies rolled in one closed-loop launch (additive under ABI 16; kernel: csrc/pcg_rollout_pop.hpp): what
+ * derivative-free policy search over network weights, the comparison of a set of checkpoints under the same disturbances
+ * and noise (the reference's policy_eval with its `policies` dict) and hyper-parameter sweeps need -- many policies, each
+ * on a slice of the batch.
+ * pcg_policy_pop holds P policies of IDENTICAL shape: n_in, n_out, n_hidden, widths, activation, output map and clip box
+ * are shared, members differ in weights and biases alone.  float64 only.  `cfg` is pcg_policy_create()'s with W[l] / b[l]
+ * pointing at P consecutive matrices / bias vectors (member-major: member m's layer l starts at W[l] + m rows cols).
+ * Storage: one device allocation of P member blocks at a fixed stride, each what pcg_policy_create() writes for one policy.
+ * pcg_policy_pop_create: PCG_E_NULL for out / cfg == NULL, PCG_E_DIM for P < 1, then pcg_policy_validate()'s statuses for
+ *   the shape and for every member's values -- all before the device is touched.  Copies to the current device
+ *   (synchronous); a population belongs to that device.
+ * pcg_policy_pop_update: rewrites members [first, first + count) from arrays holding `count` members, into the existing
+ *   allocation (nothing is allocated or freed on the device); synchronous and ordered like pcg_policy_update().  The
+ *   statuses of create for (cfg, count); PCG_E_DIM for a range outside the population or another shape; PCG_E_VALUE for
+ *   another activation, output map or clip box.  On any error the population is unchanged.
+ * pcg_policy_pop_size: P (PCG_E_NULL / PCG_E_PLAN for what is not a population). */
+typedef struct pcg_policy_pop pcg_policy_pop;
+PCG_API int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P);
+PCG_API int pcg_policy_pop_update(pcg_policy_pop* pop, const pcg_policy_cfg* cfg, int32_t first, int32_t count);
+PCG_API int pcg_policy_pop_destroy(pcg_policy_pop* pop);
+PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
+
+/* pcg_rollout_policy with one member of `pop` per slice of the batch: env e is driven by member
+ *     m = (env_offset + e) / envs_per_policy          (env_offset: pcg_plan_set_env_offset -- the GLOBAL env index, so that
+ *                                                      a sharded batch splits a population the way it splits the RNG)
+ * and computes, for its env, exactly what pcg_rollout_policy computes with that member as its policy: the same loop, the
+ * same policy arithmetic, the same rows in a_seq_out / obs_seq / rew_seq / io (each optional, strided as there).
+ * ret_out [B] (device) or NULL: each env's discounted return of THIS call's steps, accumulated in a register,
+ *     J = 0; disc = 1;   per step s = 0 .. T-1:   J = J + disc * rew_s;   disc = disc * gamma
+ * every operation rounded on its own (no fused multiply-add): a fixed rounding sequence, the bits of the same loop in any
+ * IEEE-754 double arithmetic.  A call at t0 > 0 returns the return of its own steps, discounted from its first.
+ * Statuses, nothing launched or written on any of them, in this order: those of pcg_rollout_policy for plan, io and the
+ * handle (PCG_E_PLAN for what is not a population of the plan's device); PCG_E_UNSUPPORTED for what pcg_rollout_policy
+ * refuses (io->t, constraint rows, per-env parameters, integrators other than PCG_INT_RK4 / PCG_INT_CV8) and for a plan
+ * with run-time compiled code (PCG_MODEL_USER, user_reward_src: its module does not carry this kernel -- nothing is
+ * compiled); PCG_E_DIM for members whose n_in / n_out are not the plan's Nobs / na; PCG_E_VALUE unless envs_per_policy and
+ * the plan's env offset are multiples of 64 (envs_per_policy >= 64, offset >= 0: a wave never spans two members);
+ * PCG_E_DIM unless (env_offset + B - 1) / envs_per_policy < P (B need not be a multiple of envs_per_policy); PCG_E_VALUE
+ * for a gamma that is not finite or outside [0, 1]; then T / t0 / buffers / strides as in pcg_rollout_policy.
+ * Reads the plan and the population and writes neither: no lazy allocation, no memset -- safe under stream capture.
+ * Not here: stochastic actors over a population, float32 members, plans with constraint rows or per-env parameters. */
+PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
+                                   int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                                   double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                   int64_t rew_step_stride, int32_t record_next_action, double gamma, double* ret_out,
+                                   uint64_t seed, void* stream);
+
 /* pcg_step followed, in the same launch, by the reset of every env that finished in it (gymnasium "same-step"
  * auto-reset: rew / done / viol are those of the finished step; x, obs, t, a_save and the per-env parameters are
  * those of the new episode, drawn with `reset_seed`).  Equivalent to pcg_step + pcg_reset(mask = io->done,

@@ -218,6 +218,11 @@ EXPORTS = [
     "pcg_actor_logp_const",
     "pcg_policy_noise",
     "pcg_gae",
+    "pcg_policy_pop_create",
+    "pcg_policy_pop_update",
+    "pcg_policy_pop_destroy",
+    "pcg_policy_pop_size",
+    "pcg_rollout_policy_pop",
     "pcg_step_autoreset",
     "pcg_graph_create",
     "pcg_graph_launch",
@@ -308,6 +313,18 @@ def declare(lib):
     lib.pcg_gae.restype = C.c_int
     lib.pcg_gae.argtypes = [C.c_int64, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_double, C.c_double, C.c_int32,
                             vp, C.c_int64, vp, C.c_int64, vp]
+    lib.pcg_policy_pop_create.restype = C.c_int
+    lib.pcg_policy_pop_create.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg), C.c_int32]
+    lib.pcg_policy_pop_update.restype = C.c_int
+    lib.pcg_policy_pop_update.argtypes = [vp, C.POINTER(pcg_policy_cfg), C.c_int32, C.c_int32]
+    lib.pcg_policy_pop_destroy.restype = C.c_int
+    lib.pcg_policy_pop_destroy.argtypes = [vp]
+    lib.pcg_policy_pop_size.restype = C.c_int
+    lib.pcg_policy_pop_size.argtypes = [vp]
+    # (pcg_rollout_policy's list with envs_per_policy after the handle and gamma / ret_out ahead of the seed)
+    lib.pcg_rollout_policy_pop.restype = C.c_int
+    lib.pcg_rollout_policy_pop.argtypes = (lib.pcg_rollout_policy.argtypes[:3] + [C.c_int64] + lib.pcg_rollout_policy.argtypes[3:-2]
+                                           + [C.c_double, vp] + lib.pcg_rollout_policy.argtypes[-2:])
     lib.pcg_step_autoreset.restype = C.c_int
     lib.pcg_step_autoreset.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_uint64, C.c_uint64, vp]
     lib.pcg_graph_create.restype = C.c_int

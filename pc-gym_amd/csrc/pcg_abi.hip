@@ -1809,6 +1809,119 @@ int pcg_policy_destroy(pcg_policy* q) {
   return (int)e;
 }
 
+// ---- a population of policies of one shape (pcg_rollout_pop.hpp) ---------------------------------------------------------
+struct pcg_policy_pop {
+  uint32_t magic;
+  int device;
+  int32_t P;
+  int n_in, n_out, n_hidden, width[2];  // the shape every member has, and pcg_policy_pop_update holds a new cfg against
+  int act, out_map;                     // ... with the activation, the output map and its box: members differ in weights alone
+  double out_lo, out_hi;
+  size_t blob_doubles;                  // size of ONE member's block (pack_policy's): the stride between members
+  double* dP;                           // P member blocks, one allocation
+};
+static constexpr uint32_t POP_MAGIC = 0x50434751u;  // 'PCGQ'
+
+// the cfg of member m of `count` consecutive ones behind a validated-in-shape cfg (member-major matrices and biases)
+static pcg_policy_cfg pop_member_cfg(const pcg_policy_cfg* c, int64_t m) {
+  pcg_policy_cfg one = *c;
+  for (int l = 0; l <= c->n_hidden; ++l) {
+    int rows, cols;
+    policy_layer_dims(c, l, &rows, &cols);
+    one.W[l] = c->W[l] + (size_t)m * rows * cols;
+    one.b[l] = c->b[l] + (size_t)m * rows;
+  }
+  return one;
+}
+
+// pcg_policy_validate's rules for each of `count` members (the first member's status decides the shape), host only
+static int pop_validate(const pcg_policy_cfg* cfg, int64_t count) {
+  if (!cfg) return PCG_E_NULL;
+  if (count < 1) return PCG_E_DIM;
+  PCG_TRY(pcg_policy_validate(cfg));
+  for (int64_t m = 1; m < count; ++m) {
+    const pcg_policy_cfg one = pop_member_cfg(cfg, m);
+    PCG_TRY(pcg_policy_validate(&one));
+  }
+  return PCG_OK;
+}
+
+// the blocks of `count` members, back to back
+static std::vector<double> pack_pop(const pcg_policy_cfg* cfg, int64_t count, size_t* member_doubles) {
+  std::vector<double> all;
+  for (int64_t m = 0; m < count; ++m) {
+    const pcg_policy_cfg one = pop_member_cfg(cfg, m);
+    const std::vector<double> blob = pack_policy(&one);
+    *member_doubles = blob.size();
+    all.insert(all.end(), blob.begin(), blob.end());
+  }
+  return all;
+}
+
+int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P) {
+  if (!out) return PCG_E_NULL;
+  *out = nullptr;
+  PCG_TRY(pop_validate(cfg, P));
+  pcg_policy_pop* q = new (std::nothrow) pcg_policy_pop();
+  if (!q) return (int)hipErrorOutOfMemory;
+  const std::vector<double> all = pack_pop(cfg, P, &q->blob_doubles);
+  q->P = P;
+  q->n_in = cfg->n_in; q->n_out = cfg->n_out; q->n_hidden = cfg->n_hidden;
+  for (int l = 0; l < 2; ++l) q->width[l] = l < cfg->n_hidden ? cfg->width[l] : 0;
+  q->act = cfg->activation; q->out_map = cfg->out_map;
+  q->out_lo = cfg->out_low; q->out_hi = cfg->out_high;
+  hipError_t e = hipGetDevice(&q->device);
+  if (e == hipSuccess) e = hipMalloc((void**)&q->dP, sizeof(double) * all.size());
+  if (e == hipSuccess) e = hipMemcpy(q->dP, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (q->dP) (void)hipFree(q->dP);
+    delete q;
+    return (int)e;
+  }
+  q->magic = POP_MAGIC;
+  *out = q;
+  return PCG_OK;
+}
+
+int pcg_policy_pop_update(pcg_policy_pop* q, const pcg_policy_cfg* cfg, int32_t first, int32_t count) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  PCG_TRY(pop_validate(cfg, count));
+  if (first < 0 || (int64_t)first + count > q->P) return PCG_E_DIM;
+  if (cfg->n_in != q->n_in || cfg->n_out != q->n_out || cfg->n_hidden != q->n_hidden) return PCG_E_DIM;
+  for (int l = 0; l < cfg->n_hidden; ++l)
+    if (cfg->width[l] != q->width[l]) return PCG_E_DIM;
+  if (cfg->activation != q->act || cfg->out_map != q->out_map) return PCG_E_VALUE;
+  if (cfg->out_map == PCG_POL_CLIP && (cfg->out_low != q->out_lo || cfg->out_high != q->out_hi)) return PCG_E_VALUE;
+  size_t member = 0;
+  const std::vector<double> all = pack_pop(cfg, count, &member);
+  if (member != q->blob_doubles) return PCG_E_DIM;  // (cannot happen: the block's size is a function of the shape)
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != q->device) HIP_TRY(hipSetDevice(q->device));
+  hipError_t e = hipMemcpy(q->dP + (size_t)first * member, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice);
+  if (dev != q->device) {
+    const hipError_t e2 = hipSetDevice(dev);
+    if (e == hipSuccess) e = e2;
+  }
+  return (int)e;
+}
+
+int pcg_policy_pop_size(const pcg_policy_pop* q) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  return q->P;
+}
+
+int pcg_policy_pop_destroy(pcg_policy_pop* q) {
+  if (!q) return PCG_OK;
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  q->magic = 0;
+  const hipError_t e = hipFree(q->dP);
+  delete q;
+  return (int)e;
+}
+
 // All six closed-loop entry points (pcg_rollout_policy / pcg_rollout_actor, their _cons and _unc forms) validate through three
 // functions, read top to bottom: closed_loop_open up to the policy's size, then the head's own (policy_head; actor_head: critic,
 // tanh map, sigma), then closed_loop_launch from the step range on.  (closed_loop_launch is a template over the head's
@@ -1862,6 +1975,8 @@ static int jit_prepare_closed_loop(pcg_plan* p) {
 
 static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return p->jit_pol; }
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
+// (never asked for: pop_open refuses a plan with run-time compiled code, whose module does not carry the population kernel)
+static hipFunction_t jit_head_fn(const pcg_plan*, const PopArgs&) { return nullptr; }
 
 // Plan, buffers and policy handle; then which plans the kind's kernels carry and which kernel it is (`actor`: the head); then
 // the policy's sizes.  *fn stays null for a plan with run-time compiled code, which has no ahead-of-time kernel:
@@ -2057,6 +2172,45 @@ int pcg_rollout_policy_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy*
   const PolicyArgs pa = policy_head(q, a_seq_out, a_step_stride, a_comp_stride, record_next_action);
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   return closed_loop_launch(p, io, a, fn, ClosedLoopKind::unc, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, f32_on_jit(p, q), stream);
+}
+
+// pcg_rollout_policy_pop's sibling of closed_loop_open, with its order of refusals: plan, buffers and handle; what the base
+// kind's kernels do not carry; run-time compiled code (the population kernel is ahead-of-time only); the members' sizes; then
+// what is the population's own -- the slices (whole waves per member, a member for every env) and gamma.
+static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, int64_t G, double gamma, StepArgs* a, const void** fn) {
+  PCG_TRY(fill_args(p, io, a));
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POP_MAGIC || q->device != p->device) return PCG_E_PLAN;
+  const DevConst& c = p->hc;
+  const int ls = lean_scheme(p->integrator_id);
+  if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
+  if (p->jit_fn[0]) return PCG_E_UNSUPPORTED;
+  *fn = (const void*)kernels(p->kid).roll_policy_pop[ls];
+  if (!*fn) return PCG_E_UNSUPPORTED;
+  if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
+  if (G < 64 || G % 64 != 0 || p->env_offset < 0 || p->env_offset % 64 != 0) return PCG_E_VALUE;
+  if (io->B > 0 && (p->env_offset + io->B - 1) / G >= (int64_t)q->P) return PCG_E_DIM;
+  if (!(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0)) return PCG_E_VALUE;
+  return PCG_OK;
+}
+
+int pcg_rollout_policy_pop(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, int64_t envs_per_policy, int32_t t0,
+                           int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                           int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                           int32_t record_next_action, double gamma, double* ret_out, uint64_t seed, void* stream) {
+  StepArgs a;
+  const void* fn;
+  PCG_TRY(pop_open(p, io, q, envs_per_policy, gamma, &a, &fn));
+  PopArgs pa;
+  pa.blocks = (const PCG_CONSTANT char*)q->dP;
+  pa.stride = (int64_t)(sizeof(double) * q->blob_doubles);
+  pa.G = envs_per_policy;
+  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
+  pa.record_next = record_next_action ? 1 : 0;
+  pa.gamma = gamma;
+  pa.ret_out = ret_out;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::base, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, PCG_OK, stream);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {

@@ -1183,6 +1183,8 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_cons.hpp"
 // (... nor those of the plans with per-env parameters, which refuse run-time compiled code at creation)
 #include "pcg_rollout_unc.hpp"
+// (... nor the population form of the fp64 policy kernel, which refuses run-time compiled plans)
+#include "pcg_rollout_pop.hpp"
 #endif
 namespace pcg {
 
@@ -1192,6 +1194,7 @@ using ActFn = void (*)(const StepArgs, const ActorArgs);
 #ifndef __HIPCC_RTC__
 using PolConsFn = void (*)(const StepArgs, const PolicyArgs, const ConsArgs);
 using ActConsFn = void (*)(const StepArgs, const ActorArgs, const ConsArgs);
+using PopFn = void (*)(const StepArgs, const PopArgs);
 #endif
 
 #ifndef __HIPCC_RTC__
@@ -1250,6 +1253,7 @@ struct Kernels {
   ActConsFn roll_actor_cons[2];
   PolFn roll_policy_unc;             // the fp64 two on plans with per-env parameters (RK4; null for affine: pcg_rollout_unc.hpp)
   ActFn roll_actor_unc;
+  PopFn roll_policy_pop[2];          // roll_policy with one member of a policy population per slice of envs (pcg_rollout_pop.hpp)
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1312,6 +1316,8 @@ Kernels make_kernels() {
   // closed-loop fused rollout (pcg_rollout_policy.hpp): the two fixed-step schemes, beside their open-loop kernels
   k.roll_policy[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel<M, PCG_INT_RK4>;
   k.roll_policy[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_policy_pop[lean_scheme(PCG_INT_RK4)] = rollout_pop_policy_kernel<M, PCG_INT_RK4>;
+  k.roll_policy_pop[lean_scheme(PCG_INT_CV8)] = rollout_pop_policy_kernel<M, PCG_INT_CV8>;
   k.roll_actor[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel<M, PCG_INT_RK4>;
   k.roll_actor[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel<M, PCG_INT_CV8>;
   k.roll_policy_f32[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel_f32<M, PCG_INT_RK4>;

@@ -444,6 +444,30 @@ class VecEnv:
         return self._rollout_actor("rollout_actor_unc", ac, T, collect_obs, collect_rew, collect_actions, collect_samples, collect_logp,
                                    collect_values, record_next_action)
 
+    def rollout_population(self, pop, T, envs_per_policy, gamma=1.0, collect_obs=False, collect_rew=False, collect_actions=False,
+                           collect_returns=True, record_next_action=False):
+        """``rollout_policy`` with a :class:`~pcgym_amd.policy.PolicyPopulation`: T steps in one launch
+        (``pcg_rollout_policy_pop``), env ``e`` driven by member ``(env_offset + e) // envs_per_policy`` -- each env computes
+        what ``rollout_policy`` with that member computes, bit for bit.  Returns a dict: "a" (T [+1], na, B), "obs"
+        (T, Nobs, B), "rew" (T, B), "ret" (B,) -- None where not asked for.  "ret" is each env's discounted return of THIS
+        call's steps (``J = J + disc * rew; disc = disc * gamma`` from J = 0, disc = 1, each operation rounded on its own),
+        accumulated in the kernel: a search loop needs no T x B rewards.  ``envs_per_policy`` and the env offset must be
+        multiples of 64 and the population must have a member for every env; plans the kernel does not take (constraints,
+        per-env parameters, integrators other than rk4 / cv8, user models and expressions) raise PcgError."""
+        if self.per_env_t:
+            raise ValueError("rollout_population() is lock-stepped only")
+        s, dev, B, T = self.spec, self.device, self.B, int(T)
+        R = T + (1 if record_next_action else 0)
+        a_seq, obs_seq, rew_seq, ret = self._seq_buffers(
+            ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew), ((B,), collect_returns))
+        self._buf.d = None
+        _lib.check(self._lib.pcg_rollout_policy_pop(
+            self._plan, self._bufp, pop.handle(dev), int(envs_per_policy), self.t, T,
+            _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
+            int(bool(record_next_action)), float(gamma), _ptr(ret), self._episode_seed(), self._stream()), "pcg_rollout_policy_pop")
+        self.t += T
+        return {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "ret": ret}
+
     def policy_noise(self, t=None, out=None):
         """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the
         current episode -- same Philox keys, same bits -- for a caller that samples outside the kernel."""

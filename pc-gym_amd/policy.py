@@ -251,6 +251,213 @@ def fused_unc_ok(spec, policy):
             and policy.n_in == spec.nobs and policy.n_out == spec.na and policy.validate() == 0)
 
 
+class PolicyPopulation:
+    """P float64 :class:`MLPPolicy` networks of ONE shape, each driving its own slice of a batch: what derivative-free policy
+    search over the weights, the comparison of a set of checkpoints and hyper-parameter sweeps roll -- in ONE launch
+    (``pcg_rollout_policy_pop``, ``VecEnv.rollout_population``) instead of P launches of a few workgroups.
+
+    weights[l] : (P, n_next, n_prev) array, biases[l] : (P, n_next); activation, out_map and the clip box are shared.
+    Env ``e`` of a batch is driven by member ``(env_offset + e) // envs_per_policy`` (the global env index: a sharded batch
+    splits a population the way it splits the random streams)."""
+
+    def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0):
+        if activation not in _ACT:
+            raise ValueError(f"activation must be one of {sorted(_ACT)}, not {activation!r}")
+        if out_map not in _OUT:
+            raise ValueError(f"out_map must be one of {sorted(_OUT)}, not {out_map!r}")
+        self.weights, self.biases = self._arrays(weights, biases)
+        self.activation, self.out_map = activation, out_map
+        self.out_low, self.out_high = float(out_low), float(out_high)
+        self.P = int(self.weights[0].shape[0])
+        self.n_in, self.n_out = int(self.weights[0].shape[2]), int(self.weights[-1].shape[1])
+        self.n_hidden = len(self.weights) - 1
+        self._tensors = {}   # device -> ([W], [b]) torch tensors
+        self._handles = {}   # device index -> pcg_policy_pop*
+        self._valid = None   # validate()'s status, once asked for
+
+    @staticmethod
+    def _arrays(weights, biases):
+        """contiguous float64 (P, n_next, n_prev) / (P, n_next) arrays of one member count whose layers chain, or ValueError"""
+        ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)) for w in weights]
+        bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float64)) for b in biases]
+        if not ws or len(ws) != len(bs):
+            raise ValueError("one bias array per weight array, at least one layer")
+        if ws[0].ndim != 3 or ws[0].shape[0] < 1:
+            raise ValueError(f"layer 0: weights must be (P, n_next, n_prev) with P >= 1, not {ws[0].shape}")
+        P = ws[0].shape[0]
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            if w.ndim != 3 or w.shape[0] != P or b.shape != (P, w.shape[1]):
+                raise ValueError(f"layer {l}: weights {w.shape} (P, n_next, n_prev) do not go with biases {b.shape} for P = {P}")
+            if l and w.shape[2] != ws[l - 1].shape[1]:
+                raise ValueError(f"layer {l}: {w.shape[2]} inputs after a layer of {ws[l - 1].shape[1]} units")
+        return ws, bs
+
+    @classmethod
+    def from_policies(cls, policies):
+        """From float64 MLPPolicy objects of one shape, activation, output map and clip box (ValueError otherwise)"""
+        policies = list(policies)
+        if not policies:
+            raise ValueError("from_policies needs at least one policy")
+        p0 = policies[0]
+        for p in policies:
+            if not isinstance(p, MLPPolicy) or p.dtype != "float64":
+                raise ValueError("from_policies takes float64 MLPPolicy objects")
+            if ([w.shape for w in p.weights] != [w.shape for w in p0.weights]
+                    or (p.activation, p.out_map, p.out_low, p.out_high) != (p0.activation, p0.out_map, p0.out_low, p0.out_high)):
+                raise ValueError("the members of a population share shape, activation, output map and clip box")
+        return cls([np.stack([p.weights[l] for p in policies]) for l in range(len(p0.weights))],
+                   [np.stack([p.biases[l] for p in policies]) for l in range(len(p0.biases))],
+                   activation=p0.activation, out_map=p0.out_map, out_low=p0.out_low, out_high=p0.out_high)
+
+    def member(self, i):
+        """member ``i`` as an MLPPolicy of its own (copies of the weights)"""
+        i = int(i)
+        if not 0 <= i < self.P:
+            raise ValueError(f"member {i} of a population of {self.P}")
+        return MLPPolicy([w[i].copy() for w in self.weights], [b[i].copy() for b in self.biases], activation=self.activation,
+                         out_map=self.out_map, out_low=self.out_low, out_high=self.out_high)
+
+    # ---- the callable: torch fp64 on the observation's device, each slice with its member ----------------------------------
+    def __call__(self, obs, envs_per_policy, env_offset=0):
+        """obs (B, Nobs) -> (B, na): rows ``e`` with ``(env_offset + e) // envs_per_policy == m`` through member ``m``,
+        in MLPPolicy's arithmetic: one ``addmm`` per layer and member present -- on CPU tensors the bits of the member's own
+        ``MLPPolicy.__call__`` on its slice -- or, for whole slices on a GPU, one ``baddbmm`` per layer over all members"""
+        torch = _torch()
+        obs = torch.as_tensor(obs)
+        G, off, B = int(envs_per_policy), int(env_offset), int(obs.shape[0])
+        if G < 1 or off < 0:
+            raise ValueError(f"envs_per_policy must be positive and env_offset non-negative, not {G} / {off}")
+        if B and (off + B - 1) // G >= self.P:
+            raise ValueError(f"envs {off} .. {off + B - 1} in slices of {G} need {(off + B - 1) // G + 1} members, the population has {self.P}")
+        key = str(obs.device)
+        if key not in self._tensors:
+            self._tensors[key] = ([torch.as_tensor(w, device=obs.device) for w in self.weights],
+                                  [torch.as_tensor(b, device=obs.device) for b in self.biases])
+        Ws, bs = self._tensors[key]
+        if obs.is_cuda and B and off % G == 0 and B % G == 0:
+            # whole slices on a GPU: one batched product per layer over the members present
+            m0, n = off // G, B // G
+            h = obs.to(torch.float64).reshape(n, G, self.n_in)
+            for l in range(self.n_hidden + 1):
+                h = torch.baddbmm(bs[l][m0:m0 + n].unsqueeze(1), h, Ws[l][m0:m0 + n].transpose(1, 2))
+                if l < self.n_hidden:
+                    h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
+            h = h.reshape(B, self.n_out)
+            if self.out_map == "clip":
+                h = torch.clamp(h, self.out_low, self.out_high)
+            elif self.out_map == "tanh":
+                h = torch.tanh(h)
+            return h
+        out = torch.empty((B, self.n_out), dtype=torch.float64, device=obs.device)
+        e = 0
+        while e < B:
+            m = (off + e) // G
+            e1 = min(B, (m + 1) * G - off)
+            h = obs[e:e1].to(torch.float64)
+            for l in range(self.n_hidden + 1):
+                h = torch.addmm(bs[l][m], h, Ws[l][m].t())
+                if l < self.n_hidden:
+                    h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
+            if self.out_map == "clip":
+                h = torch.clamp(h, self.out_low, self.out_high)
+            elif self.out_map == "tanh":
+                h = torch.tanh(h)
+            out[e:e1] = h
+            e = e1
+        return out
+
+    def update_(self, weights, biases, first=0):
+        """New weights for members ``first .. first + count - 1`` (``count`` = the arrays' leading size), in place: host
+        arrays, cached torch tensors and every live device handle (``pcg_policy_pop_update``: the device blocks are
+        rewritten, nothing is allocated or freed).  Another shape or a range outside the population raises ValueError and
+        leaves the population as it was."""
+        ws, bs = self._arrays(weights, biases)
+        first, count = int(first), int(ws[0].shape[0])
+        if ([w.shape[1:] for w in ws] != [w.shape[1:] for w in self.weights] or first < 0 or first + count > self.P):
+            raise ValueError(f"update_ keeps the shape {[w.shape[1:] for w in self.weights]} and stays inside the {self.P} members: "
+                             f"{[w.shape for w in ws]} at first = {first}")
+        cfg, keep = self._cfg(ws, bs)
+        lib = _lib.load()
+        for m in range(count):  # (host only: the judge of the contents, before anything changes)
+            one, keep1 = self._cfg([w[m:] for w in ws], [b[m:] for b in bs])
+            _lib.check(lib.pcg_policy_validate(C.byref(one)), "pcg_policy_validate")
+        for l in range(len(ws)):
+            self.weights[l][first:first + count] = ws[l]
+            self.biases[l][first:first + count] = bs[l]
+        self._tensors = {}
+        self._valid = 0 if self._valid == 0 else None  # (the new members were validated above)
+        for h in self._handles.values():
+            _lib.check(lib.pcg_policy_pop_update(h, C.byref(cfg), first, count), "pcg_policy_pop_update")
+        return self
+
+    # ---- the C ABI side ------------------------------------------------------------------------------------------------
+    def _cfg(self, ws, bs):
+        cfg = abi.pcg_policy_cfg()
+        cfg.n_in, cfg.n_out, cfg.n_hidden = self.n_in, self.n_out, self.n_hidden
+        for l in range(min(self.n_hidden, 2)):
+            cfg.width[l] = int(ws[l].shape[1])
+        cfg.activation, cfg.out_map = _ACT[self.activation], _OUT[self.out_map]
+        cfg.out_low, cfg.out_high = self.out_low, self.out_high
+        pd = C.POINTER(C.c_double)
+        ws, bs = [np.ascontiguousarray(w) for w in ws], [np.ascontiguousarray(b) for b in bs]
+        for l in range(min(len(ws), 3)):
+            cfg.W[l] = ws[l].ctypes.data_as(pd)
+            cfg.b[l] = bs[l].ctypes.data_as(pd)
+        return cfg, [ws, bs]
+
+    def to_cfg(self):
+        """(pcg_policy_cfg with member-major arrays, keep-alive list): what ``pcg_policy_pop_create`` takes beside ``P``"""
+        return self._cfg(self.weights, self.biases)
+
+    def validate(self):
+        """0 when the device form can hold every member (host only), else the first failing status of pcg_policy_validate"""
+        if self._valid is None:  # (remembered until update_: a search loop asks before every launch)
+            lib = _lib.load()
+            self._valid = 0
+            for m in range(self.P):
+                one, keep = self._cfg([w[m:] for w in self.weights], [b[m:] for b in self.biases])
+                rc = int(lib.pcg_policy_validate(C.byref(one)))
+                if rc != 0:
+                    self._valid = rc
+                    break
+        return self._valid
+
+    def handle(self, device):
+        """the pcg_policy_pop* of this population on `device` (created at first use, kept until close())"""
+        torch = _torch()
+        device = torch.device(device)
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in self._handles:
+            cfg, keep = self.to_cfg()
+            h = C.c_void_p()
+            with torch.cuda.device(idx):
+                _lib.check(_lib.load().pcg_policy_pop_create(C.byref(h), C.byref(cfg), self.P), "pcg_policy_pop_create")
+            self._handles[idx] = h
+        return self._handles[idx]
+
+    def close(self):
+        for h in self._handles.values():
+            _lib.load().pcg_policy_pop_destroy(h)
+        self._handles = {}
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def fused_pop_ok(spec, pop, envs_per_policy):
+    """the plans, populations and slices pcg_rollout_policy_pop takes (include/pcgym_hip.h): a built-in plan (no user model,
+    no reward or constraint expression: the run-time compiled module does not carry the population kernel), fixed-step
+    RK4 / CV8, no constraint rows, no per-env parameters; members of the plan's sizes that the device form can hold; slices
+    of whole waves (a multiple of 64 envs)"""
+    G = int(envs_per_policy)
+    return (isinstance(pop, PolicyPopulation) and spec.integrator in ("rk4", "cv8") and not spec.ncon and not spec.nunc
+            and not _runtime_compiled(spec) and G >= 64 and G % 64 == 0
+            and pop.n_in == spec.nobs and pop.n_out == spec.na and pop.validate() == 0)
+
+
 def _runtime_compiled(spec):
     """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
     return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)

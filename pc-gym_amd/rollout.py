@@ -27,7 +27,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .policy import fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_unc_ok
+from .policy import (fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_pop_ok,
+                     fused_unc_ok)
 
 
 def _torch():
@@ -184,6 +185,52 @@ def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
     if g is not None:
         out["g"] = g
     return out
+
+
+def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
+    """Score a :class:`~pcgym_amd.policy.PolicyPopulation` on a VecEnv: reset, one episode (N - 1 steps), env ``e`` driven by
+    member ``(env.env_offset + e) // envs_per_policy`` -- the evaluation step of an evolution strategy, a cross-entropy search
+    or a comparison of checkpoints under the same disturbances and noise.
+
+    Returns {"ret": (B,) each env's discounted return, "score": (P_local,) the mean of ``ret`` over each member's envs}, for
+    the members this env's slice of the global batch touches, in ascending order (the last member may have fewer envs).
+
+    Route: ONE launch (``pcg_rollout_policy_pop``, the returns accumulated in the kernel) when ``fused_pop_ok`` and the env
+    offset is a multiple of 64; otherwise -- or with ``fused=False`` -- one ``env.step`` per step with the population's
+    callable form and the kernel's recurrence in torch (``J = J + disc * rew; disc = disc * gamma``).  ``fused=True`` raises
+    ValueError where the one launch is not possible."""
+    torch = _torch()
+    s = env.spec
+    B, G, off = env.B, int(envs_per_policy), int(env.env_offset)
+    if env.per_env_t:
+        raise ValueError("evaluate_population needs a lock-stepped VecEnv")
+    if pop.n_in != s.nobs or pop.n_out != s.na:
+        raise ValueError(f"the members map {pop.n_in} -> {pop.n_out}, the env {s.nobs} -> {s.na}")
+    if G < 1 or (off + B - 1) // G >= pop.P:
+        raise ValueError(f"envs {off} .. {off + B - 1} in slices of {G} need {(off + B - 1) // max(G, 1) + 1} members, the population has {pop.P}")
+    if not (0.0 <= float(gamma) <= 1.0):
+        raise ValueError(f"gamma must be within [0, 1], not {gamma}")
+    ok = fused_pop_ok(s, pop, G) and off % 64 == 0
+    if fused and not ok:
+        raise ValueError("this plan / population / slice size does not qualify for the fused call (fused_pop_ok)")
+    T = s.N - 1
+    obs, _ = env.reset()
+    if ok and fused is not False:
+        ret = env.rollout_population(pop, T, G, gamma=gamma)["ret"]
+    else:
+        ret = torch.zeros(B, dtype=torch.float64, device=env.device)
+        disc = 1.0
+        for _ in range(T):
+            obs, rew, _, _, _ = env.step(pop(obs, G, off))
+            ret = ret + disc * rew
+            disc = disc * float(gamma)
+    # the mean over each member's envs: member m holds the envs [m G - off, (m + 1) G - off) of this batch
+    if off % G == 0 and B % G == 0:
+        return {"ret": ret, "score": ret.view(-1, G).mean(dim=1)}
+    m0, m1 = off // G, (off + B - 1) // G
+    bounds = [max(0, m * G - off) for m in range(m0, m1 + 1)] + [B]
+    score = torch.stack([ret[bounds[i]:bounds[i + 1]].mean() for i in range(len(bounds) - 1)])
+    return {"ret": ret, "score": score}
 
 
 def _gae_fusable(rew, val, term):
