@@ -780,6 +780,14 @@ PCG_API int pcg_graph_create(pcg_graph** out, pcg_plan* plan, const pcg_buffers*
 PCG_API int pcg_graph_launch(pcg_graph* graph, void* stream);
 PCG_API int pcg_graph_set_seed(pcg_graph* graph, uint64_t seed);
 PCG_API int pcg_graph_destroy(pcg_graph* graph);
+/* Rows that carry nothing new are stored once: a recorded step of the lean pipelined kernel (lock-stepped plans with none
+ * of the extras, RK4 / CV8) that directly follows another one skips the observation's set-point / disturbance slot rows
+ * when the schedules give both steps bitwise the same values, and the done bytes when both steps set the same flag.  The
+ * first recorded step stores everything, so a replay never depends on what the buffers held before it, and after every
+ * node every buffer holds exactly the bytes T pcg_step calls would have left.  *slot_nodes / *done_nodes (either may be
+ * NULL): how many recorded steps skip the slot rows / the done bytes; both 0 for graphs of any other kernel and with
+ * PCG_NO_HELD_ROWS set in the environment when the plan was created. */
+PCG_API int pcg_graph_held(const pcg_graph* graph, int32_t* slot_nodes, int32_t* done_nodes);
 
 /* Compiler output of the most recent failed run-time compilation in this process (static storage, "" if none). */
 PCG_API const char* pcg_last_jit_log(void);

@@ -228,6 +228,7 @@ EXPORTS = [
     "pcg_graph_launch",
     "pcg_graph_set_seed",
     "pcg_graph_destroy",
+    "pcg_graph_held",
     "pcg_last_jit_log",
     "pcg_philox4x32_10",
     "pcg_test_sort_tile",
@@ -336,6 +337,8 @@ def declare(lib):
     lib.pcg_graph_set_seed.argtypes = [vp, C.c_uint64]
     lib.pcg_graph_destroy.restype = C.c_int
     lib.pcg_graph_destroy.argtypes = [vp]
+    lib.pcg_graph_held.restype = C.c_int
+    lib.pcg_graph_held.argtypes = [vp, _pi, _pi]
     lib.pcg_last_jit_log.restype = C.c_char_p
     lib.pcg_last_jit_log.argtypes = []
     lib.pcg_test_sort_tile.restype = C.c_int

@@ -125,12 +125,14 @@ struct pcg_plan {
   int q_tile1[2];          // the largest tile with ONE workgroup per CU (Rodas4: launches that fit one tile per CU)
   // reference paths the tests select through the environment, read at creation: PCG_NO_FIXUP (guarded plans in one
   // launch), PCG_NO_FLAT (the single-kernel rollout), PCG_Q_FORCE_LEAN (the lean queue layout wherever it fits)
-  bool no_fixup, no_flat, q_force_lean;
+  // ... and PCG_NO_HELD_ROWS: recorded step graphs store every row in every node (pcg_graph_create; A/B)
+  bool no_fixup, no_flat, q_force_lean, no_held;
   int64_t env_offset;
   DevConst hc;       // host copy
   DevConst* dC;      // device copy
   double* dsched;    // [nsp+nd][N]
   LeanStep* dlean;   // [N] wave-uniform values of each lock-stepped step (inside the dsched allocation)
+  std::vector<LeanStep> hlean;  // host copy of that table: pcg_graph_create compares consecutive steps' slot values
   int cfg_nu;        // na + ndm as the caller counts them
   hipFunction_t jit_fn[2];  // run-time compiled general step kernel with user expressions [per_env_t] (or null)
   hipFunction_t jit_integ, jit_rhs;  // PCG_MODEL_USER: the run-time compiled test hooks (pcg_integrate / pcg_rhs)
@@ -1033,6 +1035,7 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   p->no_fixup = std::getenv("PCG_NO_FIXUP") != nullptr;
   p->no_flat = std::getenv("PCG_NO_FLAT") != nullptr;
   p->q_force_lean = std::getenv("PCG_Q_FORCE_LEAN") != nullptr;
+  p->no_held = std::getenv("PCG_NO_HELD_ROWS") != nullptr;
   p->nx = cfg->nx;  // (every other field starts zeroed)
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&p->num_cus, hipDeviceAttributeMultiprocessorCount, p->device);
@@ -1047,8 +1050,8 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   if (e == hipSuccess) e = hipMalloc((void**)&p->dsched, sched_alloc);
   if (e == hipSuccess) {
     p->dlean = reinterpret_cast<LeanStep*>(p->dsched + lean_off);
-    const std::vector<LeanStep> lt = lean_table(p->hc, cfg);
-    e = hipMemcpy(p->dlean, lt.data(), sizeof(LeanStep) * lt.size(), hipMemcpyHostToDevice);
+    p->hlean = lean_table(p->hc, cfg);
+    e = hipMemcpy(p->dlean, p->hlean.data(), sizeof(LeanStep) * p->hlean.size(), hipMemcpyHostToDevice);
   }
   if (e == hipSuccess) e = hipMemcpy(p->dC, &p->hc, sizeof(DevConst), hipMemcpyHostToDevice);
   if (e == hipSuccess && cfg->nsp)
@@ -1316,6 +1319,10 @@ static bool launch_queue(const pcg_plan* p, const Kernels& k, StepArgs a, int pe
 }
 
 // ---- pcg_step: the routes, tried in this order by step_impl; each says whether it took the launch (*rc: its status) ----
+// which of them did, as step_impl reports it (ROUTE_LEAN_PIPE: step_lean's pipelined kernel, not its auto-reset
+// instantiation; ROUTE_LEAN: any other kernel of step_lean)
+enum StepRoute { ROUTE_NONE = 0, ROUTE_JIT, ROUTE_UNC, ROUTE_QUEUE, ROUTE_LEAN_PIPE, ROUTE_LEAN, ROUTE_FEAT, ROUTE_CLASSIC };
+
 struct StepCall {
   const pcg_plan* p;
   const Kernels& k;
@@ -1326,6 +1333,8 @@ struct StepCall {
   int block;              // workgroup and dynamic LDS of the one-env-per-lane kernels
   size_t shmem;
   hipStream_t st;
+  int32_t held;           // StepArgs::held for the pipelined lean kernel, should it take the launch (pcg_graph_create)
+  StepRoute route;        // out: the route that took the launch
 };
 
 // run-time compiled general kernel with the plan's user expressions
@@ -1396,6 +1405,12 @@ static bool step_lean(StepCall& s, int* rc) {
   if (p->stream_bpc > 0 && p->stream_bpc <= occ) bpc = p->stream_bpc;
   const int64_t grid = std::min((int64_t)p->num_cus * bpc, (io->B + BLOCK * (e + 1) - 1) / (BLOCK * (e + 1)));
   s.a.nt_stores = p->nt_stores;
+  // rows the previous node of a step graph left with this step's bytes: only the pipelined kernel skips them, and its
+  // auto-reset instantiation never does
+  if (piped && !s.auto_reset) {
+    s.a.held = s.held;
+    s.route = ROUTE_LEAN_PIPE;
+  }
   hipLaunchKernelGGL(cov(fn), dim3((unsigned)grid), dim3(BLOCK), 0, s.st, s.a);
   return taken(rc, (int)hipGetLastError());
 }
@@ -1466,8 +1481,10 @@ static int step_classic(StepCall& s) {
   return rc;
 }
 
+// held: StepArgs::held, honoured by step_lean's pipelined kernel alone (internal: pcg_graph_create); *route: who took the launch
 static int step_impl(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, void* stream, bool auto_reset,
-                     uint64_t reset_seed) {
+                     uint64_t reset_seed, int32_t held = 0, StepRoute* route = nullptr) {
+  if (route) *route = ROUTE_NONE;
   StepArgs a;
   int rc = fill_args(p, io, &a);
   if (rc != PCG_OK) return rc;
@@ -1482,14 +1499,29 @@ static int step_impl(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t see
   a.auto_reset = auto_reset ? 1 : 0; a.reset_seed = reset_seed;
   const Kernels& k = kernels(p->kid);
   const bool lds_st = lds_stages_on(p, k);
-  StepCall s{p, k, io, a, per_env_t ? 1 : 0, lds_st, has_extras(c, io), auto_reset, 0, 0, (hipStream_t)stream};
+  StepCall s{p, k, io, a, per_env_t ? 1 : 0, lds_st, has_extras(c, io), auto_reset, 0, 0, (hipStream_t)stream, held, ROUTE_NONE};
   s.block = classic_shape(p, k, lds_st, &s.shmem);
   if (per_env_t) {
     const size_t sb = sched_in_lds_bytes(c, s.shmem);
     s.a.sched_in_lds = sb > 0;
     s.shmem += sb;
   }
-  if (step_jit(s, &rc) || step_unc(s, &rc) || step_queue(s, &rc) || step_lean(s, &rc) || step_feat(s, &rc)) return rc;
+  static const struct {
+    bool (*take)(StepCall&, int*);
+    StepRoute route;
+  } routes[] = {{step_jit, ROUTE_JIT},
+                {step_unc, ROUTE_UNC},
+                {step_queue, ROUTE_QUEUE},
+                {step_lean, ROUTE_LEAN},  // (or ROUTE_LEAN_PIPE: step_lean says so itself)
+                {step_feat, ROUTE_FEAT}};
+  for (const auto& r : routes) {
+    s.route = r.route;
+    if (r.take(s, &rc)) {
+      if (route) *route = s.route;
+      return rc;
+    }
+  }
+  if (route) *route = ROUTE_CLASSIC;
   return step_classic(s);
 }
 
@@ -2363,9 +2395,32 @@ struct pcg_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
   int n_nodes;
+  int slot_nodes, done_nodes;  // recorded steps that skip the observation's slot rows / the done bytes (pcg_graph_held)
 };
 static constexpr uint32_t GRAPH_MAGIC = 0x50434747u;  // 'PCGG'
 
+// What the step t of a lock-stepped lean plan would store again unchanged if it ran directly after step t - 1 on the same
+// buffers (StepArgs::held): bit 0 -- the observation's set-point and disturbance slot rows, bitwise equal in the two steps'
+// LeanStep records (memcmp: a NaN schedule value equals itself); bit 1 -- the done bytes, t + 1 == N - 1 in both or neither.
+static int32_t held_rows(const pcg_plan* p, int32_t t) {
+  const DevConst& c = p->hc;
+  if (p->no_held || p->hlean.empty() || t < 1) return 0;
+  const int last = (int)p->hlean.size() - 1;
+  const LeanStep& L = p->hlean[(size_t)std::min(t, last)];
+  const LeanStep& Lp = p->hlean[(size_t)std::min(t - 1, last)];
+  const size_t nso = (size_t)std::min(std::max(c.nsp_obs, 0), PCG_MAX_NSP), nd = (size_t)std::min(std::max(c.nd, 0), PCG_MAX_NDM);
+  int32_t held = 0;
+  if (std::memcmp(L.osp, Lp.osp, sizeof(double) * nso) == 0 && std::memcmp(L.od, Lp.od, sizeof(double) * nd) == 0) held |= 1;
+  if ((t + 1 == c.N - 1) == (t == c.N - 1)) held |= 2;
+  return held;
+}
+
+// Rows that carry nothing new are not stored twice: a node that runs step_lean's pipelined kernel directly after another
+// one that did skips the stores of held_rows().  Node 0 of the steps never skips anything, with or without with_reset (the
+// reset kernel writes other slot values and no done bytes), so a replay does not depend on what the buffers held before
+// it.  INVARIANT: after every node every buffer holds exactly the bytes it would hold with every store made -- replays
+// are bit-identical to T pcg_step calls, and a concurrent reader of the buffers sees no difference either.
+// PCG_NO_HELD_ROWS (read at plan creation) records every store (A/B measurement, tests).
 int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const double* const* a_steps,
                      const double* const* d_steps, int32_t t0, int32_t T, uint64_t seed, int with_reset) {
   if (!out) return PCG_E_NULL;
@@ -2387,10 +2442,17 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
     return (int)e;
   }
   if (with_reset) rc = pcg_reset(p, &b, nullptr, seed, cs);
+  int slot_nodes = 0, done_nodes = 0;
+  StepRoute prev = ROUTE_NONE;
   for (int j = 0; j < T && rc == PCG_OK; ++j) {
     b.a = a_steps[j];
     b.d = d_steps ? d_steps[j] : nullptr;
-    rc = pcg_step(p, &b, t0 + j, seed, cs);
+    const int32_t held = (j > 0 && prev == ROUTE_LEAN_PIPE) ? held_rows(p, t0 + j) : 0;
+    rc = step_impl(p, &b, t0 + j, seed, cs, false, 0, held, &prev);
+    if (prev == ROUTE_LEAN_PIPE) {  // (any other route ignores `held`)
+      slot_nodes += held & 1;
+      done_nodes += (held >> 1) & 1;
+    }
   }
   e = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);
@@ -2416,7 +2478,16 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
   q->graph = g;
   q->exec = ex;
   q->n_nodes = T + (with_reset ? 1 : 0);
+  q->slot_nodes = slot_nodes;
+  q->done_nodes = done_nodes;
   *out = q;
+  return PCG_OK;
+}
+
+int pcg_graph_held(const pcg_graph* q, int32_t* slot_nodes, int32_t* done_nodes) {
+  if (!q || q->magic != GRAPH_MAGIC) return PCG_E_PLAN;
+  if (slot_nodes) *slot_nodes = q->slot_nodes;
+  if (done_nodes) *done_nodes = q->done_nodes;
   return PCG_OK;
 }
 

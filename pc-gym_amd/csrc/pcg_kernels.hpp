@@ -183,6 +183,9 @@ struct StepArgs {
   int32_t fixup;         // guarded plans in two launches (pcg_abi.hip): 1 = the general kernel leaves an env the guard does not
                          // trust untouched and marks it (done[e] = PCG_DONE_PENDING), the work-queue kernel then integrates
                          // exactly the marked envs with the adaptive pair and finishes their step
+  int32_t held;          // step_kernel_pipe inside a recorded step graph (pcg_graph_create), 0 everywhere else: bit 0 = the
+                         // observation's set-point / disturbance slot rows already hold this step's values, bit 1 = the
+                         // done bytes do (the previous node stored the same bytes): those stores are skipped
   // barrier-free rollout of a guarded plan in two passes (pcg_rollout_flat.hpp): plan-owned work space
   int32_t* flat_q;       // [4] counters: [1] length of the hand-over list, [2] head of the second pass's queue
   int32_t* flat_hot;     // [B] the envs the first pass handed over (in the order they tripped)

@@ -172,7 +172,8 @@ struct Rows {
 };
 // The rows of one observation, in the order every kernel of the family writes them: ox[0..nx), then the set-point slots
 // osp[0..nso) and the disturbance slots od[0..nd), which are wave-uniform (LeanStep in constant memory, or scalars of the
-// caller).  put_state_rows: the same with the state row xs[i] going back in place ahead of each ox[i].
+// caller).  put_state_rows: the same with the state row xs[i] going back in place ahead of each ox[i]; `hold` (wave-uniform)
+// leaves the slot rows as they are -- they already hold these values (StepArgs::held bit 0).
 template <class M, int EPL, class Lane, class SP, class D>
 PCG_DEV void put_slot_rows(const Rows obs, const Lane at, int nx, int nso, int nd, const SP& osp, const D& od) {
 #pragma unroll
@@ -192,14 +193,17 @@ PCG_DEV void put_obs_rows(const Rows obs, const Lane at, int nx, int nso, int nd
 }
 template <class M, int EPL, class Lane, class SP, class D>
 PCG_DEV void put_state_rows(const Rows x, const Rows obs, const Lane at, int nx, int nso, int nd, const Pack<EPL> (&xs)[M::NX],
-                            const Pack<EPL> (&ox)[M::NX], const SP& osp, const D& od) {
+                            const Pack<EPL> (&ox)[M::NX], const SP& osp, const D& od, bool hold = false) {
 #pragma unroll
   for (int i = 0; i < M::NX; ++i)
     if (i < nx) {
       put<EPL>(at(x.base + (size_t)i * x.stride), xs[i].v, x.nt);
       put<EPL>(at(obs.base + (size_t)i * obs.stride), ox[i].v, obs.nt);
     }
-  put_slot_rows<M, EPL>(obs, at, nx, nso, nd, osp, od);
+  if (!hold) {
+    put_slot_rows<M, EPL>(obs, at, nx, nso, nd, osp, od);
+    asm volatile("");  // keep it a (scalar) branch
+  }
 }
 
 // the wave-uniform done flag of the lane's envs, EPL == 2 as one 2-byte store
@@ -234,17 +238,27 @@ PCG_DEV void flag_nonfinite(uint8_t* status, E e0, const Pack<W> (&x)[NX]) {
     if (nonfinite<NX, W>(x, j)) status[e0 + j] = PCG_ST_NONFINITE;
 }
 
-// stores of one lean tile: the state back in place, observation / reward (non-temporal on request), done flags
-template <class M, int EPL>
+// stores of one lean tile: the state back in place, observation / reward (non-temporal on request), done flags.
+// HOLD (step_kernel_pipe without the reset path): StepArgs::held names wave-uniform rows that the previous node of a step
+// graph left with these very bytes and that are not stored again -- bit 0 the observation's slot rows, bit 1 the done flags.
+// The word passes through an empty asm here, in the tile loop: its two tests then stay in the loop and the kernel carries
+// ONE scalar register for them.  Hoisted, each outcome is a scalar pair of its own, and the headline kernel, one register
+// short of the scalar file as it is, spilled four of them into a new vector register (58 -> 59).
+template <class M, int EPL, bool HOLD = false>
 PCG_DEV void store_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, uint32_t e0,
                         const Pack<EPL> (&xs)[M::NX], const LeanOut<M, EPL>& out, bool nt) {
   const size_t B = (size_t)A.B;
   const int nx = M::DYNAMIC ? c.nx : M::NX;
   const LaneOff8 at{e0 * 8u};
+  int32_t held = HOLD ? A.held : 0;
+  if (HOLD) asm volatile("" : "+s"(held));
   put_state_rows<M, EPL>(Rows{A.x, B, (A.nt_stores & 2) != 0}, Rows{A.obs, B, nt}, at, nx, c.nsp_obs, c.nd, xs, out.ox,
-                         L.osp, L.od);
+                         L.osp, L.od, (held & 1) != 0);
   put<EPL>(at(A.rew), out.rew.v, nt);
-  put_done<EPL>(A.done + e0, out.done);
+  if (!(held & 2)) {
+    put_done<EPL>(A.done + e0, out.done);
+    asm volatile("");  // keep it a (scalar) branch
+  }
 }
 
 // initial state of one env (pcgym.py:284-288, apply_uncertainties :255-261) and its observation rows: the draws of
@@ -460,7 +474,7 @@ __global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) voi
         put_done<EPL>(A.done + e0, true);
         reset_lean<M, EPL>(A, c, (int64_t)e0, A.reset_seed, nt);
       } else {
-        store_lean<M, EPL>(A, c, L, e0, xs, out, nt);
+        store_lean<M, EPL, !AR>(A, c, L, e0, xs, out, nt);  // (the auto-reset instantiation stores everything)
       }
     }
     PCG_TL(3);

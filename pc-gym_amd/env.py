@@ -551,6 +551,17 @@ class StepGraph:
                                                  int(self.with_reset)), "pcg_graph_create")
         self._g = g
 
+    @property
+    def held(self):
+        """(slot_nodes, done_nodes): how many recorded steps skip the stores of the observation's set-point /
+        disturbance slot rows, and of the done bytes, because the step recorded before them left the same bytes there
+        (pcg_graph_held)."""
+        if self._g is None:
+            raise RuntimeError("StepGraph was destroyed")
+        ns, nd = C.c_int32(0), C.c_int32(0)
+        _lib.check(self.env._lib.pcg_graph_held(self._g, C.byref(ns), C.byref(nd)), "pcg_graph_held")
+        return ns.value, nd.value
+
     def replay(self):
         """Run the recorded steps on the current stream; returns (obs, rew, done) of the last one."""
         env = self.env
