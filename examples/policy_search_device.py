@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Derivative-free policy search with the weights born, scored and refitted ON the device: the cross-entropy method of
+examples/policy_search.py, then an antithetic evolution strategy, on the canonical cstr.
+
+Every generation is a handful of launches and no weight crosses PCIe after the first one:
+
+  * PolicyPopulation.sample_ draws the 256 members of a diagonal Gaussian straight into the packed device blocks
+    (pcg_policy_pop_sample: Philox + Box-Muller keyed by seed, generation, member and parameter);
+  * evaluate_population scores each member on its own 256 envs -- 65,536 envs, ONE launch (pcg_rollout_policy_pop);
+  * CEM  : PolicyPopulation.flat(members=elite) gathers the best tenth as flat parameter vectors, the refit is two torch
+           reductions on the device;
+    ES   : centered_ranks(score) weights the noise, PolicyPopulation.noise_dot forms sum_m w_m z(m, .) from the SAME keys
+           (pcg_policy_pop_noise_dot: the noise is never stored), the update is one torch statement.
+
+Needs an MI355X (there is no CPU path):  python examples/policy_search_device.py [iterations]
+"""
+import copy
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden")]
+import scenarios as SC  # noqa: E402
+from pcgym_amd import PolicyPopulation, centered_ranks, evaluate_population, make_vec_env  # noqa: E402
+
+P, G, HIDDEN = 256, 256, 16
+SEED = 2024
+
+
+def main():
+    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
+    p.update(integrator="rk4")
+    env = make_vec_env(p, n_envs=P * G, seed=0)
+    spec, dev = env.spec, env.device
+    dims = [spec.nobs, HIDDEN, spec.na]
+    # the device blocks are allocated once, from zeros; every generation rewrites them in place
+    pop = PolicyPopulation([np.zeros((P, dims[l + 1], dims[l])) for l in range(len(dims) - 1)],
+                           [np.zeros((P, dims[l + 1])) for l in range(len(dims) - 1)],
+                           activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+    pop.handle(dev)
+    n = pop.n_params
+    what = f"({P} members x {G} envs, {spec.N - 1} steps, one launch; {n} parameters per member, none crossed to the host)"
+
+    # ---- cross-entropy method: refit the Gaussian to the best tenth ----
+    mean = torch.zeros(n, dtype=torch.float64, device=dev)
+    std = torch.full((n,), 0.5, dtype=torch.float64, device=dev)
+    for it in range(iters):
+        pop.sample_(mean, std, SEED, generation=it, check=False)
+        score = evaluate_population(env, pop, G, gamma=1.0)["score"]
+        elite = torch.topk(score, P // 10).indices
+        theta = pop.flat(members=elite)
+        mean, std = theta.mean(dim=0), theta.std(dim=0, unbiased=False) + 0.02
+        print(f"CEM iteration {it}: best score {float(score.max()):10.4f}   mean score {float(score.mean()):10.4f}   {what}")
+
+    # ---- antithetic evolution strategy with centered ranks, from where CEM stopped ----
+    sigma, lr = 0.1, 0.05
+    std = torch.full((n,), sigma, dtype=torch.float64, device=dev)
+    for it in range(iters):
+        gen = iters + it  # (generations already used above keyed other noise)
+        pop.sample_(mean, std, SEED, generation=gen, antithetic=True, check=False)
+        score = evaluate_population(env, pop, G, gamma=1.0)["score"]
+        grad = pop.noise_dot(centered_ranks(score), SEED, generation=gen, antithetic=True)  # sum_m w_m z(m, .)
+        mean = mean + (lr / (P * sigma)) * grad
+        print(f"ES  iteration {it}: best score {float(score.max()):10.4f}   mean score {float(score.mean()):10.4f}   {what}")
+
+    best = pop.member(int(torch.argmax(score)))  # (the first look at the host arrays: one flat() and one copy bring them back)
+    print(f"best member of the last generation: layers {[w.shape for w in best.weights]}, |W0| max {np.abs(best.weights[0]).max():.3f}")
+    env.close(), pop.close()
+
+
+if __name__ == "__main__":
+    main()

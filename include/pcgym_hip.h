@@ -756,6 +756,62 @@ PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const 
                                    int64_t rew_step_stride, int32_t record_next_action, double gamma, double* ret_out,
                                    uint64_t seed, void* stream);
 
+/* The weights of a population written and read ON the device (additive under ABI 16; kernels: csrc/pcg_pop_search.hpp):
+ * what surrounds pcg_rollout_policy_pop in a derivative-free search loop -- sampling the members of a diagonal Gaussian,
+ * the score-weighted noise sum of an evolution strategy, and flat parameter vectors in and out of the packed blocks --
+ * with no weight crossing to the host.
+ *
+ * Flat parameter order.  Parameter j of a member, 0 <= j < n, runs layer by layer: W[l] row-major (n_next x n_prev)
+ * followed by b[l]; n = sum_l rows_l (cols_l + 1) = pcg_policy_pop_nparams().  No entry point below writes a member's
+ * header or padding.
+ *
+ * Search noise (the engine's RNG contract, purpose PCG_RNG_SEARCH; no existing stream uses that word).  For member m (the
+ * population's own index: global across shards), parameter j, `generation` g and `seed`:
+ *     q = antithetic ? m >> 1 : m
+ *     o = philox4x32_10(ctr = (q, j >> 2, g, PCG_RNG_SEARCH), key = (seed_lo, seed_hi))
+ *     (z0, z1) = box_muller_f32(o[0], o[1]) -> parameters 4b, 4b + 1       (b = j >> 2)
+ *     (z2, z3) = box_muller_f32(o[2], o[3]) -> parameters 4b + 2, 4b + 3
+ *     z(m, j)  = (double) of that float, negated (exactly) when antithetic and m is odd
+ * Variates past n in the last block are discarded.
+ *
+ * pcg_policy_pop_sample: members [first, first + count): theta(m, j) = mean[j] + std[j] * z(m, j), product and sum each
+ *   rounded on their own (no fused multiply-add), written into the packed blocks in place.  Other members are not touched.
+ *   mean, std: device arrays [n].
+ * pcg_policy_pop_noise_dot: out[j] = sum over m in [first, first + count) of w[m - first] * z(m, j), in a FIXED order:
+ *   chunks of PCG_POP_CHUNK consecutive members counted from `first`; within a chunk acc = 0.0, then acc = acc + (w * z) for
+ *   ascending m (two roundings each); partial[c][j] = acc; out[j] = 0.0 + partial[0][j] + partial[1][j] + ... ascending.
+ *   w: device [count]; partial: caller-provided device workspace of ceil(count / PCG_POP_CHUNK) * n doubles; out: device
+ *   [n].  Two launches, no atomics: the same bits for every launch shape.  The noise is formed again from the keys, never
+ *   stored.
+ * pcg_policy_pop_get_flat: theta[i * theta_member_stride + j] = parameter j of member (members ? members[i] : first + i),
+ *   i < count.  members: device array [count] or NULL, repeats allowed (`first` is not read when it is given); an index
+ *   outside [0, P) writes NaN into that row and nothing else -- no fault, no host read.
+ * pcg_policy_pop_set_flat: the inverse for the range [first, first + count): the device-to-device form of
+ *   pcg_policy_pop_update().
+ *
+ * Statuses, decided before anything is launched, in this order: PCG_E_NULL for a NULL pop or a NULL required pointer
+ * (mean, std; w, partial, out; theta); PCG_E_PLAN for what is not a population, or a population of a device other than the
+ * caller's current one; PCG_E_DIM for count < 1, first < 0, first + count > P (with `members`: count < 1 alone), or a member
+ * stride < n; PCG_E_VALUE for antithetic not 0 or 1.
+ * The CONTENTS of device arrays are not inspected (that would be a host read): a non-finite mean, std or theta gives
+ * non-finite weights in exactly those members, where pcg_policy_pop_update() would have refused them.  What
+ * pcg_rollout_policy_pop then does with such a member: its outputs are NaN (PCG_POL_CLIP keeps a NaN), so the envs it drives
+ * go non-finite -- their states, observations, rewards and ret_out entries are NaN and io->status, where given, reports
+ * PCG_ST_NONFINITE.  The envs of every other member are computed as ever; nothing faults.
+ * No allocation, no memset, no synchronisation in any of the five: the launches go to `stream` and are safe under stream
+ * capture.  Not here: full-covariance sampling, float32 members, a device-side generation counter. */
+#define PCG_RNG_SEARCH 0x500
+#define PCG_POP_CHUNK 64
+PCG_API int pcg_policy_pop_nparams(const pcg_policy_pop* pop);
+PCG_API int pcg_policy_pop_sample(pcg_policy_pop* pop, int32_t first, int32_t count, const double* mean, const double* std,
+                                  int32_t antithetic, uint64_t seed, uint32_t generation, void* stream);
+PCG_API int pcg_policy_pop_noise_dot(const pcg_policy_pop* pop, int32_t first, int32_t count, int32_t antithetic, uint64_t seed,
+                                     uint32_t generation, const double* w, double* partial, double* out, void* stream);
+PCG_API int pcg_policy_pop_get_flat(const pcg_policy_pop* pop, const int32_t* members, int32_t first, int32_t count,
+                                    double* theta, int64_t theta_member_stride, void* stream);
+PCG_API int pcg_policy_pop_set_flat(pcg_policy_pop* pop, int32_t first, int32_t count, const double* theta,
+                                    int64_t theta_member_stride, void* stream);
+
 /* pcg_step followed, in the same launch, by the reset of every env that finished in it (gymnasium "same-step"
  * auto-reset: rew / done / viol are those of the finished step; x, obs, t, a_save and the per-env parameters are
  * those of the new episode, drawn with `reset_seed`).  Equivalent to pcg_step + pcg_reset(mask = io->done,

@@ -10,7 +10,7 @@ from .gather import HostGather  # noqa: F401
 from .mixed import MixedVecEnv, make_mixed_sharded_env, mixed_shard_layout  # noqa: F401
 from .policy import GaussianActorCritic, MLPPolicy, PolicyPopulation  # noqa: F401
 from .reference_engine import hip_integration_engine  # noqa: F401
-from .rollout import collect_onpolicy, collect_rollouts, evaluate_population, gae, reproducibility_metric  # noqa: F401
+from .rollout import centered_ranks, collect_onpolicy, collect_rollouts, evaluate_population, gae, reproducibility_metric  # noqa: F401
 from .spaces import Box  # noqa: F401
 
 __version__ = "0.1.0"

@@ -75,6 +75,8 @@ PCG_POL_MAX_WIDTH = 64
 PCG_POL_F64 = 0
 PCG_POL_F32 = 1
 PCG_RNG_POLICY = 0x400
+PCG_RNG_SEARCH = 0x500
+PCG_POP_CHUNK = 64
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -223,6 +225,11 @@ EXPORTS = [
     "pcg_policy_pop_destroy",
     "pcg_policy_pop_size",
     "pcg_rollout_policy_pop",
+    "pcg_policy_pop_nparams",
+    "pcg_policy_pop_sample",
+    "pcg_policy_pop_noise_dot",
+    "pcg_policy_pop_get_flat",
+    "pcg_policy_pop_set_flat",
     "pcg_step_autoreset",
     "pcg_graph_create",
     "pcg_graph_launch",
@@ -326,6 +333,17 @@ def declare(lib):
     lib.pcg_rollout_policy_pop.restype = C.c_int
     lib.pcg_rollout_policy_pop.argtypes = (lib.pcg_rollout_policy.argtypes[:3] + [C.c_int64] + lib.pcg_rollout_policy.argtypes[3:-2]
                                            + [C.c_double, vp] + lib.pcg_rollout_policy.argtypes[-2:])
+    # (the weights of a population on the device: sample, noise sum, flat vectors out and in)
+    lib.pcg_policy_pop_nparams.restype = C.c_int
+    lib.pcg_policy_pop_nparams.argtypes = [vp]
+    lib.pcg_policy_pop_sample.restype = C.c_int
+    lib.pcg_policy_pop_sample.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_uint64, C.c_uint32, vp]
+    lib.pcg_policy_pop_noise_dot.restype = C.c_int
+    lib.pcg_policy_pop_noise_dot.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp]
+    lib.pcg_policy_pop_get_flat.restype = C.c_int
+    lib.pcg_policy_pop_get_flat.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int64, vp]
+    lib.pcg_policy_pop_set_flat.restype = C.c_int
+    lib.pcg_policy_pop_set_flat.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64, vp]
     lib.pcg_step_autoreset.restype = C.c_int
     lib.pcg_step_autoreset.argtypes = [vp, C.POINTER(pcg_buffers), C.c_int32, C.c_uint64, C.c_uint64, vp]
     lib.pcg_graph_create.restype = C.c_int

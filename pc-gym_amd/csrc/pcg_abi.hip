@@ -4,6 +4,7 @@
 #include "pcg_kernels.hpp"
 #include "pcg_step_feat.hpp"
 #include "pcg_gae.hpp"
+#include "pcg_pop_search.hpp"
 
 #include <hip/hiprtc.h>
 #include <dirent.h>
@@ -1851,6 +1852,7 @@ struct pcg_policy_pop {
   double out_lo, out_hi;
   size_t blob_doubles;                  // size of ONE member's block (pack_policy's): the stride between members
   double* dP;                           // P member blocks, one allocation
+  PopLayout lay;                        // where the flat parameters of a member live in its block (pcg_pop_search.hpp)
 };
 static constexpr uint32_t POP_MAGIC = 0x50434751u;  // 'PCGQ'
 
@@ -1864,6 +1866,32 @@ static pcg_policy_cfg pop_member_cfg(const pcg_policy_cfg* c, int64_t m) {
     one.b[l] = c->b[l] + (size_t)m * rows;
   }
   return one;
+}
+
+// The flat parameter order of a member (pcg_pop_search.hpp) against the block pack_policy wrote for it: W[l] row-major, then
+// b[l], layer by layer; offsets in doubles from the block's start.
+static PopLayout pop_layout(const pcg_policy_cfg* c, const double* block) {
+  PolicyDev h;
+  std::memcpy(&h, block, sizeof(h));
+  constexpr int HDR = (int)(sizeof(PolicyDev) / sizeof(double));
+  PopLayout L;
+  std::memset(&L, 0, sizeof(L));
+  L.nl = c->n_hidden + 1;
+  int n = 0;
+  for (int l = 0; l <= c->n_hidden; ++l) {
+    int rows, cols;
+    policy_layer_dims(c, l, &rows, &cols);
+    L.start[l] = n;
+    L.rows[l] = rows;
+    L.cols[l] = cols;
+    L.ld[l] = h.ld[l];
+    L.offW[l] = HDR + h.offW[l];
+    L.offb[l] = HDR + h.offb[l];
+    n += rows * (cols + 1);
+  }
+  for (int l = c->n_hidden + 1; l < 4; ++l) L.start[l] = n;
+  L.n = n;
+  return L;
 }
 
 // pcg_policy_validate's rules for each of `count` members (the first member's status decides the shape), host only
@@ -1898,6 +1926,7 @@ int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32
   if (!q) return (int)hipErrorOutOfMemory;
   const std::vector<double> all = pack_pop(cfg, P, &q->blob_doubles);
   q->P = P;
+  q->lay = pop_layout(cfg, all.data());
   q->n_in = cfg->n_in; q->n_out = cfg->n_out; q->n_hidden = cfg->n_hidden;
   for (int l = 0; l < 2; ++l) q->width[l] = l < cfg->n_hidden ? cfg->width[l] : 0;
   q->act = cfg->activation; q->out_map = cfg->out_map;
@@ -1943,6 +1972,97 @@ int pcg_policy_pop_size(const pcg_policy_pop* q) {
   if (!q) return PCG_E_NULL;
   if (q->magic != POP_MAGIC) return PCG_E_PLAN;
   return q->P;
+}
+
+// ---- the weights of a population written and read on the device (pcg_pop_search.hpp) -------------------------------------
+// what all five decide first: a population, of the caller's current device
+static int pop_search_open(const pcg_policy_pop* q) {
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != q->device) return PCG_E_PLAN;
+  return PCG_OK;
+}
+static bool pop_range_ok(const pcg_policy_pop* q, int32_t first, int32_t count) {
+  return count >= 1 && first >= 0 && (int64_t)first + count <= q->P;
+}
+// grid of the kernels that run blockIdx.x over `lanes` lanes of one row and stride blockIdx.y over `rows` rows
+static dim3 pop_grid(int64_t lanes, int64_t rows) {
+  return dim3((unsigned)((lanes + POP_BLOCK - 1) / POP_BLOCK), (unsigned)std::min<int64_t>(rows, POP_MAX_GRID_Y));
+}
+
+int pcg_policy_pop_nparams(const pcg_policy_pop* q) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  return q->lay.n;
+}
+
+int pcg_policy_pop_sample(pcg_policy_pop* q, int32_t first, int32_t count, const double* mean, const double* std,
+                          int32_t antithetic, uint64_t seed, uint32_t generation, void* stream) {
+  if (!q || !mean || !std) return PCG_E_NULL;
+  PCG_TRY(pop_search_open(q));
+  if (!pop_range_ok(q, first, count)) return PCG_E_DIM;
+  if (antithetic != 0 && antithetic != 1) return PCG_E_VALUE;
+  PopSampleArgs a;
+  a.L = q->lay;
+  a.blocks = q->dP;
+  a.stride = (int64_t)q->blob_doubles;
+  a.first = first; a.count = count; a.antithetic = antithetic;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.g = generation;
+  a.mean = mean; a.std = std;
+  hipLaunchKernelGGL(cov(pop_sample_kernel), pop_grid((q->lay.n + 3) / 4, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int pcg_policy_pop_noise_dot(const pcg_policy_pop* q, int32_t first, int32_t count, int32_t antithetic, uint64_t seed,
+                             uint32_t generation, const double* w, double* partial, double* out, void* stream) {
+  static_assert(POP_CHUNK == PCG_POP_CHUNK, "chunk of the fixed summation order");
+  if (!q || !w || !partial || !out) return PCG_E_NULL;
+  PCG_TRY(pop_search_open(q));
+  if (!pop_range_ok(q, first, count)) return PCG_E_DIM;
+  if (antithetic != 0 && antithetic != 1) return PCG_E_VALUE;
+  PopDotArgs a;
+  a.n = q->lay.n;
+  a.first = first; a.count = count; a.antithetic = antithetic;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.g = generation;
+  a.w = w; a.partial = partial; a.out = out;
+  const int64_t chunks = ((int64_t)count + POP_CHUNK - 1) / POP_CHUNK;
+  hipLaunchKernelGGL(cov(pop_noise_dot_kernel), pop_grid((a.n + 3) / 4, chunks), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(cov(pop_chunk_sum_kernel), pop_grid(a.n, 1), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int pcg_policy_pop_get_flat(const pcg_policy_pop* q, const int32_t* members, int32_t first, int32_t count, double* theta,
+                            int64_t theta_member_stride, void* stream) {
+  if (!q || !theta) return PCG_E_NULL;
+  PCG_TRY(pop_search_open(q));
+  if (members ? count < 1 : !pop_range_ok(q, first, count)) return PCG_E_DIM;
+  if (theta_member_stride < q->lay.n) return PCG_E_DIM;
+  PopFlatArgs a;
+  a.L = q->lay;
+  a.blocks = q->dP;
+  a.stride = (int64_t)q->blob_doubles;
+  a.P = q->P; a.first = members ? 0 : first; a.count = count;
+  a.members = members;
+  a.theta = theta; a.theta_stride = theta_member_stride;
+  hipLaunchKernelGGL(cov(pop_get_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int pcg_policy_pop_set_flat(pcg_policy_pop* q, int32_t first, int32_t count, const double* theta, int64_t theta_member_stride,
+                            void* stream) {
+  if (!q || !theta) return PCG_E_NULL;
+  PCG_TRY(pop_search_open(q));
+  if (!pop_range_ok(q, first, count)) return PCG_E_DIM;
+  if (theta_member_stride < q->lay.n) return PCG_E_DIM;
+  PopFlatArgs a;
+  a.L = q->lay;
+  a.blocks = q->dP;
+  a.stride = (int64_t)q->blob_doubles;
+  a.P = q->P; a.first = first; a.count = count;
+  a.members = nullptr;
+  a.theta = const_cast<double*>(theta); a.theta_stride = theta_member_stride;
+  hipLaunchKernelGGL(cov(pop_set_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
 }
 
 int pcg_policy_pop_destroy(pcg_policy_pop* q) {

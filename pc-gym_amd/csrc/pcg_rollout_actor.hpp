@@ -22,6 +22,7 @@
 namespace pcg {
 
 constexpr uint32_t RNG_POLICY = 0x400u;  // purpose of the policy's exploration noise, beside RNG_NOISE / RNG_DIST / RNG_RESET
+constexpr uint32_t RNG_SEARCH = 0x500u;  // purpose of the search noise over a population's weights (pcg_pop_search.hpp)
 
 struct ActorArgs {
   const PCG_CONSTANT PolicyDev* P;   // actor

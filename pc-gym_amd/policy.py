@@ -258,7 +258,15 @@ class PolicyPopulation:
 
     weights[l] : (P, n_next, n_prev) array, biases[l] : (P, n_next); activation, out_map and the clip box are shared.
     Env ``e`` of a batch is driven by member ``(env_offset + e) // envs_per_policy`` (the global env index: a sharded batch
-    splits a population the way it splits the random streams)."""
+    splits a population the way it splits the random streams).
+
+    The weights can also be written and read ON the device, in the flat parameter order of :meth:`flat_layout`
+    (include/pcgym_hip.h, csrc/pcg_pop_search.hpp): :meth:`sample_` draws members of a diagonal Gaussian straight into the
+    packed blocks, :meth:`noise_dot` forms an evolution strategy's score-weighted noise sum from the same keys,
+    :meth:`flat` / :meth:`set_flat_` move flat parameter vectors out and in.  After a device-side write the host arrays
+    ``weights`` / ``biases`` are stale for those members; everything that reads them (``member``, the callable, ``to_cfg``,
+    ``update_``, ``close``) first brings them back with one :meth:`flat` and one copy.  A population never written from the
+    device behaves as it always did."""
 
     def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0):
         if activation not in _ACT:
@@ -274,6 +282,8 @@ class PolicyPopulation:
         self._tensors = {}   # device -> ([W], [b]) torch tensors
         self._handles = {}   # device index -> pcg_policy_pop*
         self._valid = None   # validate()'s status, once asked for
+        self._stale = None   # (P,) bool: members whose host arrays are behind the device (None: never written from the device)
+        self._stale_dev = None  # index of the device that holds them
 
     @staticmethod
     def _arrays(weights, biases):
@@ -314,6 +324,7 @@ class PolicyPopulation:
         i = int(i)
         if not 0 <= i < self.P:
             raise ValueError(f"member {i} of a population of {self.P}")
+        self._refresh()
         return MLPPolicy([w[i].copy() for w in self.weights], [b[i].copy() for b in self.biases], activation=self.activation,
                          out_map=self.out_map, out_low=self.out_low, out_high=self.out_high)
 
@@ -329,6 +340,7 @@ class PolicyPopulation:
             raise ValueError(f"envs_per_policy must be positive and env_offset non-negative, not {G} / {off}")
         if B and (off + B - 1) // G >= self.P:
             raise ValueError(f"envs {off} .. {off + B - 1} in slices of {G} need {(off + B - 1) // G + 1} members, the population has {self.P}")
+        self._refresh()
         key = str(obs.device)
         if key not in self._tensors:
             self._tensors[key] = ([torch.as_tensor(w, device=obs.device) for w in self.weights],
@@ -371,6 +383,7 @@ class PolicyPopulation:
         arrays, cached torch tensors and every live device handle (``pcg_policy_pop_update``: the device blocks are
         rewritten, nothing is allocated or freed).  Another shape or a range outside the population raises ValueError and
         leaves the population as it was."""
+        self._refresh()
         ws, bs = self._arrays(weights, biases)
         first, count = int(first), int(ws[0].shape[0])
         if ([w.shape[1:] for w in ws] != [w.shape[1:] for w in self.weights] or first < 0 or first + count > self.P):
@@ -407,11 +420,16 @@ class PolicyPopulation:
 
     def to_cfg(self):
         """(pcg_policy_cfg with member-major arrays, keep-alive list): what ``pcg_policy_pop_create`` takes beside ``P``"""
+        self._refresh()
         return self._cfg(self.weights, self.biases)
 
     def validate(self):
-        """0 when the device form can hold every member (host only), else the first failing status of pcg_policy_validate"""
+        """0 when the device form can hold every member (host only), else the first failing status of pcg_policy_validate.
+        Remembered: a device-side write keeps the shape, and the values it writes are not inspected (include/pcgym_hip.h says
+        what a rollout does with a non-finite member), so it leaves a remembered 0 standing and a search loop reads nothing
+        back between generations."""
         if self._valid is None:  # (remembered until update_: a search loop asks before every launch)
+            self._refresh()
             lib = _lib.load()
             self._valid = 0
             for m in range(self.P):
@@ -436,6 +454,7 @@ class PolicyPopulation:
         return self._handles[idx]
 
     def close(self):
+        self._refresh()  # (the device blocks go: what was written there comes back first)
         for h in self._handles.values():
             _lib.load().pcg_policy_pop_destroy(h)
         self._handles = {}
@@ -445,6 +464,200 @@ class PolicyPopulation:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+    # ---- the weights on the device: flat parameter vectors, sampling, the noise sum ------------------------------------------
+    @property
+    def n_params(self):
+        """parameters per member: sum over the layers of rows (cols + 1)"""
+        return sum(int(w.shape[1]) * (int(w.shape[2]) + 1) for w in self.weights)
+
+    def flat_layout(self):
+        """[(name, l, start, stop, shape)] in flat parameter order: layer by layer ``("W", l, ...)`` with the matrix row-major
+        (n_next, n_prev), then ``("b", l, ...)`` -- parameter ``j`` of :meth:`flat` is entry ``j - start`` of that array.
+        Host only."""
+        out, j = [], 0
+        for l, w in enumerate(self.weights):
+            rows, cols = int(w.shape[1]), int(w.shape[2])
+            out.append(("W", l, j, j + rows * cols, (rows, cols)))
+            j += rows * cols
+            out.append(("b", l, j, j + rows, (rows,)))
+            j += rows
+        return out
+
+    def _search_device(self, device=None, write=False):
+        """index of the device the flat entry points work on: `device`, else the one with a live handle, else the current
+        one.  A device-side write needs the population to live on no other device."""
+        torch = _torch()
+        if device is not None:
+            device = torch.device(device)
+            idx = device.index if device.index is not None else torch.cuda.current_device()
+        elif self._stale_dev is not None and self._stale is not None and self._stale.any():
+            idx = self._stale_dev
+        elif len(self._handles) == 1:
+            idx = next(iter(self._handles))
+        elif not self._handles:
+            idx = torch.cuda.current_device()
+        else:
+            idx = torch.cuda.current_device()
+            if idx not in self._handles:
+                raise ValueError(f"the population has handles on devices {sorted(self._handles)}: make one of them current")
+        if write and any(d != idx for d in self._handles):
+            raise ValueError(f"a population with live handles on devices {sorted(self._handles)} cannot be written from device {idx}: "
+                             "a device-side write reaches one device (a sharded run is one process per device)")
+        return idx
+
+    def _as_device(self, values, idx, dtype, shape, what):
+        """`values` as a tensor of `dtype` and `shape` on device `idx` (numpy arrays and lists are copied there)"""
+        torch = _torch()
+        dev = torch.device("cuda", idx)
+        t = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values), device=dev)
+        if not t.is_cuda or t.device.index != idx:
+            raise ValueError(f"{what} lives on {t.device}, the population on {dev}")
+        if t.dtype != dtype:
+            raise ValueError(f"{what} must be {dtype}, not {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+        return t
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.P - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.P:
+            raise ValueError(f"members {first} .. {first + count - 1} of a population of {self.P}")
+        return first, count
+
+    def _written(self, idx, first, count):
+        if self._stale is None:
+            self._stale = np.zeros(self.P, dtype=bool)
+        self._stale[first:first + count] = True
+        self._stale_dev = idx
+        self._tensors = {}
+
+    def _flat(self, idx, members, first, count):
+        """(count, n) tensor on device `idx` from the device blocks (no look at the host arrays)"""
+        torch = _torch()
+        n = self.n_params
+        h = self._handles[idx]
+        theta = torch.empty((count, n), dtype=torch.float64, device=torch.device("cuda", idx))
+        with torch.cuda.device(idx):
+            rc = _lib.load().pcg_policy_pop_get_flat(h, members.data_ptr() if members is not None else None, first, count,
+                                                     theta.data_ptr(), n, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pcg_policy_pop_get_flat")
+        return theta
+
+    def _refresh(self):
+        """bring the host arrays of the members written on the device back: one flat() and one copy"""
+        if self._stale is None or not self._stale.any():
+            return
+        torch = _torch()
+        idx = self._stale_dev
+        which = np.flatnonzero(self._stale)
+        if which.size == self.P:
+            theta = self._flat(idx, None, 0, self.P)
+        else:
+            members = torch.as_tensor(which.astype(np.int32), device=torch.device("cuda", idx))
+            theta = self._flat(idx, members, 0, int(which.size))
+        theta = theta.cpu().numpy()
+        for name, l, a, b, shape in self.flat_layout():
+            (self.weights if name == "W" else self.biases)[l][which] = theta[:, a:b].reshape((-1,) + shape)
+        self._stale[:] = False
+        self._tensors = {}
+
+    def sample_(self, mean, std, seed, generation=0, antithetic=False, first=0, count=None, device=None, check=True):
+        """Members ``first .. first + count - 1`` drawn from the diagonal Gaussian N(mean, diag(std^2)) straight into the packed
+        device blocks (``pcg_policy_pop_sample``): ``theta[m, j] = mean[j] + std[j] * z(m, j)`` with the search noise of the
+        RNG contract (keyed by ``seed``, ``generation``, the member and the parameter), ``antithetic``: members
+        ``2q`` and ``2q + 1`` get ``+z`` and ``-z``.  Nothing crosses to the host and no other member is touched.
+
+        mean, std : float64 tensors of shape ``(n_params,)`` on the population's device (numpy arrays are copied there).
+        check     : True costs one reduction and one synchronisation and raises ValueError unless ``mean`` is finite and
+                    ``std`` finite and >= 0; False reads nothing back (what a captured or pipelined loop wants)."""
+        torch = _torch()
+        idx = self._search_device(device, write=True)
+        first, count = self._range(first, count)
+        n = self.n_params
+        mean = self._as_device(mean, idx, torch.float64, (n,), "mean").contiguous()
+        std = self._as_device(std, idx, torch.float64, (n,), "std").contiguous()
+        if check and not bool(torch.isfinite(mean).all() & torch.isfinite(std).all() & (std >= 0).all()):
+            raise ValueError("sample_ needs a finite mean and a finite, non-negative std")
+        if self.validate() != 0:
+            raise ValueError(f"the device form cannot hold this population (pcg_policy_validate: {self.validate()})")
+        h = self.handle(torch.device("cuda", idx))
+        with torch.cuda.device(idx):
+            rc = _lib.load().pcg_policy_pop_sample(h, first, count, mean.data_ptr(), std.data_ptr(), int(bool(antithetic)),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(generation) & 0xFFFFFFFF,
+                                                   torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pcg_policy_pop_sample")
+        self._written(idx, first, count)
+        return self
+
+    def noise_dot(self, weights, seed, generation=0, antithetic=False, first=0):
+        """``out[j] = sum_i weights[i] * z(first + i, j)``: an evolution strategy's score-weighted noise sum over the members
+        ``first .. first + len(weights) - 1``, formed from the keys :meth:`sample_` drew with -- the noise is never stored
+        (``pcg_policy_pop_noise_dot``: a fixed summation order in chunks of 64 members, the same bits for every launch).
+        weights : (count,) float64 tensor on the population's device (numpy arrays are copied).  Returns an ``(n_params,)``
+        device tensor; the workspace is allocated by torch here."""
+        torch = _torch()
+        idx = self._search_device()
+        w = self._as_device(weights, idx, torch.float64, None, "weights")
+        if w.dim() != 1:
+            raise ValueError(f"weights must be one-dimensional, not {tuple(w.shape)}")
+        w = w.contiguous()
+        first, count = self._range(first, int(w.shape[0]) if w.shape[0] else 0)
+        n = self.n_params
+        dev = torch.device("cuda", idx)
+        chunks = (count + abi.PCG_POP_CHUNK - 1) // abi.PCG_POP_CHUNK
+        partial = torch.empty((chunks, n), dtype=torch.float64, device=dev)
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        h = self.handle(dev)
+        with torch.cuda.device(idx):
+            rc = _lib.load().pcg_policy_pop_noise_dot(h, first, count, int(bool(antithetic)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                      int(generation) & 0xFFFFFFFF, w.data_ptr(), partial.data_ptr(),
+                                                      out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pcg_policy_pop_noise_dot")
+        return out
+
+    def flat(self, members=None, first=0, count=None):
+        """(count, n_params) float64 device tensor of flat parameter vectors (:meth:`flat_layout`'s order), read from the
+        packed device blocks (``pcg_policy_pop_get_flat``): members ``first .. first + count - 1``, or the rows ``members``
+        names (a sequence or an int32 / int64 tensor; repeats allowed; an index outside ``[0, P)`` gives a row of NaN)."""
+        torch = _torch()
+        idx = self._search_device()
+        dev = torch.device("cuda", idx)
+        self.handle(dev)
+        if members is None:
+            first, count = self._range(first, count)
+            return self._flat(idx, None, first, count)
+        m = members if isinstance(members, torch.Tensor) else torch.as_tensor(np.asarray(members, dtype=np.int64))
+        if m.dim() != 1 or m.shape[0] < 1 or m.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"members must be a non-empty one-dimensional integer sequence, not {tuple(m.shape)} of {m.dtype}")
+        if m.dtype == torch.int64:  # (an index that does not fit 32 bits is outside every population: it stays outside)
+            m = m.clamp(-1, 2 ** 31 - 1)
+        m = m.to(device=dev, dtype=torch.int32).contiguous()
+        return self._flat(idx, m, 0, int(m.shape[0]))
+
+    def set_flat_(self, theta, first=0):
+        """Members ``first .. first + count - 1`` from the rows of ``theta`` (count, n_params), float64 on the population's
+        device (numpy arrays are copied there): the device-to-device form of :meth:`update_` (``pcg_policy_pop_set_flat``).
+        The values are not inspected."""
+        torch = _torch()
+        idx = self._search_device(write=True)
+        t = self._as_device(theta, idx, torch.float64, None, "theta")
+        n = self.n_params
+        if t.dim() != 2 or t.shape[1] != n:
+            raise ValueError(f"theta must be (count, {n}), not {tuple(t.shape)}")
+        first, count = self._range(first, int(t.shape[0]) if t.shape[0] else 0)
+        if t.stride(1) != 1 or (count > 1 and t.stride(0) < n):
+            t = t.contiguous()
+        if self.validate() != 0:
+            raise ValueError(f"the device form cannot hold this population (pcg_policy_validate: {self.validate()})")
+        h = self.handle(torch.device("cuda", idx))
+        with torch.cuda.device(idx):
+            rc = _lib.load().pcg_policy_pop_set_flat(h, first, count, t.data_ptr(), t.stride(0) if count > 1 else n,
+                                                     torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pcg_policy_pop_set_flat")
+        self._written(idx, first, count)
+        return self
 
 
 def fused_pop_ok(spec, pop, envs_per_policy):

@@ -233,6 +233,23 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
     return {"ret": ret, "score": score}
 
 
+def centered_ranks(score):
+    """What an evolution strategy weights its noise with (Salimans et al. 2017): the rank of each entry of ``score`` (P,)
+    mapped to ``[-0.5, 0.5]`` -- the lowest score gets -0.5, the highest +0.5 -- as a float64 tensor on ``score``'s device.
+    Ties are broken by index (a stable sort), so the result is deterministic; a single entry gets 0."""
+    torch = _torch()
+    score = torch.as_tensor(score)
+    if score.dim() != 1 or score.shape[0] < 1:
+        raise ValueError(f"centered_ranks takes a non-empty one-dimensional tensor, not {tuple(score.shape)}")
+    P = int(score.shape[0])
+    order = torch.argsort(score, stable=True)
+    ranks = torch.empty(P, dtype=torch.float64, device=score.device)
+    ranks[order] = torch.arange(P, dtype=torch.float64, device=score.device)
+    if P == 1:
+        return ranks
+    return ranks / (P - 1) - 0.5
+
+
 def _gae_fusable(rew, val, term):
     """why these tensors cannot go through ``pcg_gae`` (a string), or None: float64, on one GPU, 2-D, unit stride along B --
     row-sliced or padded views qualify through their row strides"""
