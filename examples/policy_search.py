@@ -7,8 +7,12 @@ the batch is driven by its own member of a PolicyPopulation, the discounted retu
 refits the Gaussian to the best tenth.  The population's device blocks are allocated once and rewritten every iteration
 (PolicyPopulation.update_).
 
-Needs an MI355X (there is no CPU path):  python examples/policy_search.py [iterations]
+--dtype float32 holds the candidates as float32 members (rounded to nearest by the population, evaluated in float32 inside the
+kernel); the Gaussian is refitted to the float64 samples as before.
+
+Needs an MI355X (there is no CPU path):  python examples/policy_search.py [iterations] [--dtype float32]
 """
+import argparse
 import copy
 import os
 import sys
@@ -37,7 +41,11 @@ def unflatten(theta, dims):
 
 
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    ap = argparse.ArgumentParser()
+    ap.add_argument("iterations", nargs="?", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
+    args = ap.parse_args()
+    iters = args.iterations
     p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
     p.update(integrator="rk4")
     env = make_vec_env(p, n_envs=P * G, seed=0)
@@ -51,7 +59,7 @@ def main():
         theta = mean + std * rng.standard_normal((P, n))
         Ws, bs = unflatten(theta, dims)
         if pop is None:
-            pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+            pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=args.dtype)
         else:
             pop.update_(Ws, bs)
         score = evaluate_population(env, pop, G, gamma=1.0)["score"]

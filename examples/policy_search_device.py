@@ -12,8 +12,12 @@ Every generation is a handful of launches and no weight crosses PCIe after the f
     ES   : centered_ranks(score) weights the noise, PolicyPopulation.noise_dot forms sum_m w_m z(m, .) from the SAME keys
            (pcg_policy_pop_noise_dot: the noise is never stored), the update is one torch statement.
 
-Needs an MI355X (there is no CPU path):  python examples/policy_search_device.py [iterations]
+--dtype float32 searches over float32 members (pcg_policy_pop_create_f32): the same calls, the same keys and fp64 mean / std;
+each sampled parameter is stored rounded to float32 and every member is evaluated in float32 inside the kernel.
+
+Needs an MI355X (there is no CPU path):  python examples/policy_search_device.py [iterations] [--dtype float32]
 """
+import argparse
 import copy
 import os
 import sys
@@ -31,7 +35,11 @@ SEED = 2024
 
 
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    ap = argparse.ArgumentParser()
+    ap.add_argument("iterations", nargs="?", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
+    args = ap.parse_args()
+    iters = args.iterations
     p = copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"])
     p.update(integrator="rk4")
     env = make_vec_env(p, n_envs=P * G, seed=0)
@@ -40,7 +48,7 @@ def main():
     # the device blocks are allocated once, from zeros; every generation rewrites them in place
     pop = PolicyPopulation([np.zeros((P, dims[l + 1], dims[l])) for l in range(len(dims) - 1)],
                            [np.zeros((P, dims[l + 1])) for l in range(len(dims) - 1)],
-                           activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+                           activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=args.dtype)
     pop.handle(dev)
     n = pop.n_params
     what = f"({P} members x {G} envs, {spec.N - 1} steps, one launch; {n} parameters per member, none crossed to the host)"

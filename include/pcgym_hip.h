@@ -714,8 +714,9 @@ PCG_API int pcg_gae(int64_t B, int32_t T, const double* rew, int64_t rew_step_st
  * and noise (the reference's policy_eval with its `policies` dict) and hyper-parameter sweeps need -- many policies, each
  * on a slice of the batch.
  * pcg_policy_pop holds P policies of IDENTICAL shape: n_in, n_out, n_hidden, widths, activation, output map and clip box
- * are shared, members differ in weights and biases alone.  float64 only.  `cfg` is pcg_policy_create()'s with W[l] / b[l]
- * pointing at P consecutive matrices / bias vectors (member-major: member m's layer l starts at W[l] + m rows cols).
+ * are shared, members differ in weights and biases alone, and all are float64 or all float32.  `cfg` is
+ * pcg_policy_create()'s with W[l] / b[l] pointing at P consecutive matrices / bias vectors (member-major: member m's layer l
+ * starts at W[l] + m rows cols).
  * Storage: one device allocation of P member blocks at a fixed stride, each what pcg_policy_create() writes for one policy.
  * pcg_policy_pop_create: PCG_E_NULL for out / cfg == NULL, PCG_E_DIM for P < 1, then pcg_policy_validate()'s statuses for
  *   the shape and for every member's values -- all before the device is touched.  Copies to the current device
@@ -724,9 +725,20 @@ PCG_API int pcg_gae(int64_t B, int32_t T, const double* rew, int64_t rew_step_st
  *   allocation (nothing is allocated or freed on the device); synchronous and ordered like pcg_policy_update().  The
  *   statuses of create for (cfg, count); PCG_E_DIM for a range outside the population or another shape; PCG_E_VALUE for
  *   another activation, output map or clip box.  On any error the population is unchanged.
- * pcg_policy_pop_size: P (PCG_E_NULL / PCG_E_PLAN for what is not a population). */
+ * pcg_policy_pop_size: P (PCG_E_NULL / PCG_E_PLAN for what is not a population).
+ * pcg_policy_pop_create_f32: the float32 form -- every member block is what pcg_policy_create_f32() writes for one policy
+ *   (the same header, then floats: every value rounded to nearest, the rows of two consecutive units interleaved, the clip box
+ *   holding the rounded bounds), back to back at one byte stride that is a multiple of 8.  The statuses of
+ *   pcg_policy_pop_create, then PCG_E_VALUE when any member holds a value that is not finite after rounding or a clip bound
+ *   overflows: nothing is allocated.  pcg_rollout_policy_pop evaluates such members in float32 (pcg_rollout_policy's
+ *   arithmetic for a pcg_policy_create_f32 policy); the env stays fp64.
+ *   pcg_policy_pop_update on a float32 population rounds the same way, compares the clip box AFTER rounding and judges every
+ *   member of the range before a byte is copied: a member that overflows gives PCG_E_VALUE and the blocks stay as they were.
+ * pcg_policy_pop_dtype: PCG_POL_F64 | PCG_POL_F32 (PCG_E_NULL / PCG_E_PLAN for what is not a population). */
 typedef struct pcg_policy_pop pcg_policy_pop;
 PCG_API int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P);
+PCG_API int pcg_policy_pop_create_f32(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P);
+PCG_API int pcg_policy_pop_dtype(const pcg_policy_pop* pop);
 PCG_API int pcg_policy_pop_update(pcg_policy_pop* pop, const pcg_policy_cfg* cfg, int32_t first, int32_t count);
 PCG_API int pcg_policy_pop_destroy(pcg_policy_pop* pop);
 PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
@@ -735,7 +747,8 @@ PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
  *     m = (env_offset + e) / envs_per_policy          (env_offset: pcg_plan_set_env_offset -- the GLOBAL env index, so that
  *                                                      a sharded batch splits a population the way it splits the RNG)
  * and computes, for its env, exactly what pcg_rollout_policy computes with that member as its policy: the same loop, the
- * same policy arithmetic, the same rows in a_seq_out / obs_seq / rew_seq / io (each optional, strided as there).
+ * same policy arithmetic, the same rows in a_seq_out / obs_seq / rew_seq / io (each optional, strided as there).  The kernel is
+ * picked by the population's dtype: a float32 population (pcg_policy_pop_create_f32) is refused exactly where a float64 one is.
  * ret_out [B] (device) or NULL: each env's discounted return of THIS call's steps, accumulated in a register,
  *     J = 0; disc = 1;   per step s = 0 .. T-1:   J = J + disc * rew_s;   disc = disc * gamma
  * every operation rounded on its own (no fused multiply-add): a fixed rounding sequence, the bits of the same loop in any
@@ -749,7 +762,7 @@ PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
  * PCG_E_DIM unless (env_offset + B - 1) / envs_per_policy < P (B need not be a multiple of envs_per_policy); PCG_E_VALUE
  * for a gamma that is not finite or outside [0, 1]; then T / t0 / buffers / strides as in pcg_rollout_policy.
  * Reads the plan and the population and writes neither: no lazy allocation, no memset -- safe under stream capture.
- * Not here: stochastic actors over a population, float32 members, plans with constraint rows or per-env parameters. */
+ * Not here: stochastic actors over a population, plans with constraint rows or per-env parameters. */
 PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
                                    int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
                                    double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
@@ -782,7 +795,8 @@ PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const 
  *   ascending m (two roundings each); partial[c][j] = acc; out[j] = 0.0 + partial[0][j] + partial[1][j] + ... ascending.
  *   w: device [count]; partial: caller-provided device workspace of ceil(count / PCG_POP_CHUNK) * n doubles; out: device
  *   [n].  Two launches, no atomics: the same bits for every launch shape.  The noise is formed again from the keys, never
- *   stored.
+ *   stored.  The blocks are not read: on a float32 population a member's realised perturbation is
+ *   round32(mean + std z) - mean, not std z, while the sum uses the unrounded z -- an evolution strategy's ordinary noise.
  * pcg_policy_pop_get_flat: theta[i * theta_member_stride + j] = parameter j of member (members ? members[i] : first + i),
  *   i < count.  members: device array [count] or NULL, repeats allowed (`first` is not read when it is given); an index
  *   outside [0, P) writes NaN into that row and nothing else -- no fault, no host read.
@@ -798,8 +812,15 @@ PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const 
  * pcg_rollout_policy_pop then does with such a member: its outputs are NaN (PCG_POL_CLIP keeps a NaN), so the envs it drives
  * go non-finite -- their states, observations, rewards and ret_out entries are NaN and io->status, where given, reports
  * PCG_ST_NONFINITE.  The envs of every other member are computed as ever; nothing faults.
+ * A float32 population (pcg_policy_pop_create_f32) takes the same five calls with the same signatures, fp64 mean / std / theta
+ * / w, flat order and keys; only where a parameter lives and how it is stored change.  Parameter (l, r, k) sits at float offset
+ * HDR + offW[l] + ((r / 2) ld[l] + k) 2 + (r & 1) of its block and bias (l, r) at HDR + offb[l] + r, HDR the header's size in
+ * floats.  _sample forms mean[j] + std[j] * z in fp64 exactly as above and stores it with ONE round-to-nearest conversion: a
+ * float32 member is bit for bit (float) of what a float64 population holds under the same seed, generation and antithetic
+ * flag.  A value that overflows float32 is stored as +-inf and not inspected: such a member behaves as a non-finite one above.
+ * _set_flat stores (float)theta, rounded to nearest; _get_flat returns the stored float widened exactly (NaN rows as above).
  * No allocation, no memset, no synchronisation in any of the five: the launches go to `stream` and are safe under stream
- * capture.  Not here: full-covariance sampling, float32 members, a device-side generation counter. */
+ * capture.  Not here: full-covariance sampling, a device-side generation counter. */
 #define PCG_RNG_SEARCH 0x500
 #define PCG_POP_CHUNK 64
 PCG_API int pcg_policy_pop_nparams(const pcg_policy_pop* pop);

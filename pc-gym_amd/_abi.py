@@ -221,6 +221,8 @@ EXPORTS = [
     "pcg_policy_noise",
     "pcg_gae",
     "pcg_policy_pop_create",
+    "pcg_policy_pop_create_f32",
+    "pcg_policy_pop_dtype",
     "pcg_policy_pop_update",
     "pcg_policy_pop_destroy",
     "pcg_policy_pop_size",
@@ -323,6 +325,10 @@ def declare(lib):
                             vp, C.c_int64, vp, C.c_int64, vp]
     lib.pcg_policy_pop_create.restype = C.c_int
     lib.pcg_policy_pop_create.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg), C.c_int32]
+    lib.pcg_policy_pop_create_f32.restype = C.c_int
+    lib.pcg_policy_pop_create_f32.argtypes = [C.POINTER(vp), C.POINTER(pcg_policy_cfg), C.c_int32]
+    lib.pcg_policy_pop_dtype.restype = C.c_int
+    lib.pcg_policy_pop_dtype.argtypes = [vp]
     lib.pcg_policy_pop_update.restype = C.c_int
     lib.pcg_policy_pop_update.argtypes = [vp, C.POINTER(pcg_policy_cfg), C.c_int32, C.c_int32]
     lib.pcg_policy_pop_destroy.restype = C.c_int

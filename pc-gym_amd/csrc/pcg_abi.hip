@@ -1850,8 +1850,9 @@ struct pcg_policy_pop {
   int n_in, n_out, n_hidden, width[2];  // the shape every member has, and pcg_policy_pop_update holds a new cfg against
   int act, out_map;                     // ... with the activation, the output map and its box: members differ in weights alone
   double out_lo, out_hi;
-  size_t blob_doubles;                  // size of ONE member's block (pack_policy's): the stride between members
+  size_t blob_doubles;                  // size of ONE member's block (pack_policy's / pack_policy_f32's): the stride between members
   double* dP;                           // P member blocks, one allocation
+  int dtype;                            // PCG_POL_F64 | PCG_POL_F32: which packing every block holds (as pcg_policy::dtype)
   PopLayout lay;                        // where the flat parameters of a member live in its block (pcg_pop_search.hpp)
 };
 static constexpr uint32_t POP_MAGIC = 0x50434751u;  // 'PCGQ'
@@ -1869,13 +1870,16 @@ static pcg_policy_cfg pop_member_cfg(const pcg_policy_cfg* c, int64_t m) {
 }
 
 // The flat parameter order of a member (pcg_pop_search.hpp) against the block pack_policy wrote for it: W[l] row-major, then
-// b[l], layer by layer; offsets in doubles from the block's start.
-static PopLayout pop_layout(const pcg_policy_cfg* c, const double* block) {
+// b[l], layer by layer; offsets in elements from the block's start: doubles, or floats for pack_policy_f32's block, whose
+// header counts offW / offb in floats.
+static PopLayout pop_layout(const pcg_policy_cfg* c, const double* block, int dtype) {
+  static_assert(sizeof(PolicyDev) % sizeof(double) == 0, "the weights behind the header are aligned for pair loads");
   PolicyDev h;
   std::memcpy(&h, block, sizeof(h));
-  constexpr int HDR = (int)(sizeof(PolicyDev) / sizeof(double));
+  const int HDR = (int)(sizeof(PolicyDev) / (dtype == PCG_POL_F32 ? sizeof(float) : sizeof(double)));
   PopLayout L;
   std::memset(&L, 0, sizeof(L));
+  L.f32 = dtype == PCG_POL_F32 ? 1 : 0;
   L.nl = c->n_hidden + 1;
   int n = 0;
   for (int l = 0; l <= c->n_hidden; ++l) {
@@ -1906,31 +1910,42 @@ static int pop_validate(const pcg_policy_cfg* cfg, int64_t count) {
   return PCG_OK;
 }
 
-// the blocks of `count` members, back to back
-static std::vector<double> pack_pop(const pcg_policy_cfg* cfg, int64_t count, size_t* member_doubles) {
+// the blocks of `count` members, back to back (a block is whole doubles in either form: a byte stride that is a multiple
+// of 8).  *rc: PCG_E_VALUE when a member of a float32 population is not finite after rounding -- every member is judged.
+static std::vector<double> pack_pop(const pcg_policy_cfg* cfg, int64_t count, int dtype, size_t* member_doubles, int* rc) {
   std::vector<double> all;
+  *rc = PCG_OK;
   for (int64_t m = 0; m < count; ++m) {
     const pcg_policy_cfg one = pop_member_cfg(cfg, m);
-    const std::vector<double> blob = pack_policy(&one);
+    int prc = PCG_OK;
+    const std::vector<double> blob = dtype == PCG_POL_F32 ? pack_policy_f32(&one, &prc) : pack_policy(&one);
+    if (prc != PCG_OK) *rc = prc;
     *member_doubles = blob.size();
     all.insert(all.end(), blob.begin(), blob.end());
   }
   return all;
 }
 
-int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P) {
+static int pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P, int dtype) {
   if (!out) return PCG_E_NULL;
   *out = nullptr;
   PCG_TRY(pop_validate(cfg, P));
+  size_t member = 0;
+  int prc = PCG_OK;
+  const std::vector<double> all = pack_pop(cfg, P, dtype, &member, &prc);
+  PCG_TRY(prc);  // (nothing is allocated)
   pcg_policy_pop* q = new (std::nothrow) pcg_policy_pop();
   if (!q) return (int)hipErrorOutOfMemory;
-  const std::vector<double> all = pack_pop(cfg, P, &q->blob_doubles);
+  q->blob_doubles = member;
+  q->dtype = dtype;
   q->P = P;
-  q->lay = pop_layout(cfg, all.data());
+  q->lay = pop_layout(cfg, all.data(), dtype);
   q->n_in = cfg->n_in; q->n_out = cfg->n_out; q->n_hidden = cfg->n_hidden;
   for (int l = 0; l < 2; ++l) q->width[l] = l < cfg->n_hidden ? cfg->width[l] : 0;
   q->act = cfg->activation; q->out_map = cfg->out_map;
-  q->out_lo = cfg->out_low; q->out_hi = cfg->out_high;
+  // (the box update holds a new cfg against: a float32 population's is the rounded one, as in its members' headers)
+  q->out_lo = dtype == PCG_POL_F32 ? (double)(float)cfg->out_low : cfg->out_low;
+  q->out_hi = dtype == PCG_POL_F32 ? (double)(float)cfg->out_high : cfg->out_high;
   hipError_t e = hipGetDevice(&q->device);
   if (e == hipSuccess) e = hipMalloc((void**)&q->dP, sizeof(double) * all.size());
   if (e == hipSuccess) e = hipMemcpy(q->dP, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice);
@@ -1944,6 +1959,15 @@ int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32
   return PCG_OK;
 }
 
+int pcg_policy_pop_create(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P) { return pop_create(out, cfg, P, PCG_POL_F64); }
+int pcg_policy_pop_create_f32(pcg_policy_pop** out, const pcg_policy_cfg* cfg, int32_t P) { return pop_create(out, cfg, P, PCG_POL_F32); }
+
+int pcg_policy_pop_dtype(const pcg_policy_pop* q) {
+  if (!q) return PCG_E_NULL;
+  if (q->magic != POP_MAGIC) return PCG_E_PLAN;
+  return q->dtype;
+}
+
 int pcg_policy_pop_update(pcg_policy_pop* q, const pcg_policy_cfg* cfg, int32_t first, int32_t count) {
   if (!q) return PCG_E_NULL;
   if (q->magic != POP_MAGIC) return PCG_E_PLAN;
@@ -1953,9 +1977,13 @@ int pcg_policy_pop_update(pcg_policy_pop* q, const pcg_policy_cfg* cfg, int32_t 
   for (int l = 0; l < cfg->n_hidden; ++l)
     if (cfg->width[l] != q->width[l]) return PCG_E_DIM;
   if (cfg->activation != q->act || cfg->out_map != q->out_map) return PCG_E_VALUE;
-  if (cfg->out_map == PCG_POL_CLIP && (cfg->out_low != q->out_lo || cfg->out_high != q->out_hi)) return PCG_E_VALUE;
+  const bool f32 = q->dtype == PCG_POL_F32;
+  const double lo = f32 ? (double)(float)cfg->out_low : cfg->out_low, hi = f32 ? (double)(float)cfg->out_high : cfg->out_high;
+  if (cfg->out_map == PCG_POL_CLIP && (lo != q->out_lo || hi != q->out_hi)) return PCG_E_VALUE;
   size_t member = 0;
-  const std::vector<double> all = pack_pop(cfg, count, &member);
+  int prc = PCG_OK;
+  const std::vector<double> all = pack_pop(cfg, count, q->dtype, &member, &prc);
+  PCG_TRY(prc);  // (every member of the range was judged: no byte is copied)
   if (member != q->blob_doubles) return PCG_E_DIM;  // (cannot happen: the block's size is a function of the shape)
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -1985,6 +2013,10 @@ static int pop_search_open(const pcg_policy_pop* q) {
 static bool pop_range_ok(const pcg_policy_pop* q, int32_t first, int32_t count) {
   return count >= 1 && first >= 0 && (int64_t)first + count <= q->P;
 }
+// elements between two members' blocks, in the unit the layout counts in (doubles, or floats for a float32 population)
+static int64_t pop_stride(const pcg_policy_pop* q) {
+  return (int64_t)q->blob_doubles * (q->dtype == PCG_POL_F32 ? 2 : 1);
+}
 // grid of the kernels that run blockIdx.x over `lanes` lanes of one row and stride blockIdx.y over `rows` rows
 static dim3 pop_grid(int64_t lanes, int64_t rows) {
   return dim3((unsigned)((lanes + POP_BLOCK - 1) / POP_BLOCK), (unsigned)std::min<int64_t>(rows, POP_MAX_GRID_Y));
@@ -2005,11 +2037,14 @@ int pcg_policy_pop_sample(pcg_policy_pop* q, int32_t first, int32_t count, const
   PopSampleArgs a;
   a.L = q->lay;
   a.blocks = q->dP;
-  a.stride = (int64_t)q->blob_doubles;
+  a.stride = pop_stride(q);
   a.first = first; a.count = count; a.antithetic = antithetic;
   a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.g = generation;
   a.mean = mean; a.std = std;
-  hipLaunchKernelGGL(cov(pop_sample_kernel), pop_grid((q->lay.n + 3) / 4, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  if (q->dtype == PCG_POL_F32)
+    hipLaunchKernelGGL(cov(pop_sample_kernel_f32), pop_grid((q->lay.n + 3) / 4, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(cov(pop_sample_kernel), pop_grid((q->lay.n + 3) / 4, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 
@@ -2040,11 +2075,14 @@ int pcg_policy_pop_get_flat(const pcg_policy_pop* q, const int32_t* members, int
   PopFlatArgs a;
   a.L = q->lay;
   a.blocks = q->dP;
-  a.stride = (int64_t)q->blob_doubles;
+  a.stride = pop_stride(q);
   a.P = q->P; a.first = members ? 0 : first; a.count = count;
   a.members = members;
   a.theta = theta; a.theta_stride = theta_member_stride;
-  hipLaunchKernelGGL(cov(pop_get_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  if (q->dtype == PCG_POL_F32)
+    hipLaunchKernelGGL(cov(pop_get_flat_kernel_f32), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(cov(pop_get_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 
@@ -2057,11 +2095,14 @@ int pcg_policy_pop_set_flat(pcg_policy_pop* q, int32_t first, int32_t count, con
   PopFlatArgs a;
   a.L = q->lay;
   a.blocks = q->dP;
-  a.stride = (int64_t)q->blob_doubles;
+  a.stride = pop_stride(q);
   a.P = q->P; a.first = first; a.count = count;
   a.members = nullptr;
   a.theta = const_cast<double*>(theta); a.theta_stride = theta_member_stride;
-  hipLaunchKernelGGL(cov(pop_set_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  if (q->dtype == PCG_POL_F32)
+    hipLaunchKernelGGL(cov(pop_set_flat_kernel_f32), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(cov(pop_set_flat_kernel), pop_grid(a.L.n, count), dim3(POP_BLOCK), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 
@@ -2127,7 +2168,7 @@ static int jit_prepare_closed_loop(pcg_plan* p) {
 
 static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return p->jit_pol; }
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
-// (never asked for: pop_open refuses a plan with run-time compiled code, whose module does not carry the population kernel)
+// (never asked for: pop_open refuses a plan with run-time compiled code, whose module does not carry the population kernels)
 static hipFunction_t jit_head_fn(const pcg_plan*, const PopArgs&) { return nullptr; }
 
 // Plan, buffers and policy handle; then which plans the kind's kernels carry and which kernel it is (`actor`: the head); then
@@ -2337,7 +2378,7 @@ static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q,
   const int ls = lean_scheme(p->integrator_id);
   if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
   if (p->jit_fn[0]) return PCG_E_UNSUPPORTED;
-  *fn = (const void*)kernels(p->kid).roll_policy_pop[ls];
+  *fn = (const void*)(q->dtype == PCG_POL_F32 ? kernels(p->kid).roll_policy_pop_f32 : kernels(p->kid).roll_policy_pop)[ls];
   if (!*fn) return PCG_E_UNSUPPORTED;
   if (q->n_in != c.nobs || q->n_out != c.na) return PCG_E_DIM;
   if (G < 64 || G % 64 != 0 || p->env_offset < 0 || p->env_offset % 64 != 0) return PCG_E_VALUE;

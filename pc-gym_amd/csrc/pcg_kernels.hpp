@@ -1186,7 +1186,7 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_cons.hpp"
 // (... nor those of the plans with per-env parameters, which refuse run-time compiled code at creation)
 #include "pcg_rollout_unc.hpp"
-// (... nor the population form of the fp64 policy kernel, which refuses run-time compiled plans)
+// (... nor the population forms of the fp64 and float32 policy kernels, which refuse run-time compiled plans)
 #include "pcg_rollout_pop.hpp"
 #endif
 namespace pcg {
@@ -1257,6 +1257,7 @@ struct Kernels {
   PolFn roll_policy_unc;             // the fp64 two on plans with per-env parameters (RK4; null for affine: pcg_rollout_unc.hpp)
   ActFn roll_actor_unc;
   PopFn roll_policy_pop[2];          // roll_policy with one member of a policy population per slice of envs (pcg_rollout_pop.hpp)
+  PopFn roll_policy_pop_f32[2];      // ... of a float32 population (pcg_policy_pop_create_f32)
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1321,6 +1322,8 @@ Kernels make_kernels() {
   k.roll_policy[lean_scheme(PCG_INT_CV8)] = rollout_policy_kernel<M, PCG_INT_CV8>;
   k.roll_policy_pop[lean_scheme(PCG_INT_RK4)] = rollout_pop_policy_kernel<M, PCG_INT_RK4>;
   k.roll_policy_pop[lean_scheme(PCG_INT_CV8)] = rollout_pop_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_policy_pop_f32[lean_scheme(PCG_INT_RK4)] = rollout_pop_policy_kernel_f32<M, PCG_INT_RK4>;
+  k.roll_policy_pop_f32[lean_scheme(PCG_INT_CV8)] = rollout_pop_policy_kernel_f32<M, PCG_INT_CV8>;
   k.roll_actor[lean_scheme(PCG_INT_RK4)] = rollout_actor_kernel<M, PCG_INT_RK4>;
   k.roll_actor[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel<M, PCG_INT_CV8>;
   k.roll_policy_f32[lean_scheme(PCG_INT_RK4)] = rollout_policy_kernel_f32<M, PCG_INT_RK4>;

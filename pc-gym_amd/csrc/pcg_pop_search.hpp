@@ -30,6 +30,14 @@
 //   pop_get_flat_kernel /  one lane per (row, parameter); an index outside [0, P) reads as a row of NaN.
 //   pop_set_flat_kernel
 // The summation order is fixed by the chunk size alone, never by the launch shape: the same bits for every grid.
+//
+// A float32 population (pcg_policy_pop_create_f32; blocks of pack_policy_f32's form) has siblings of the three kernels that touch
+// the blocks: pop_sample_kernel_f32, pop_get_flat_kernel_f32, pop_set_flat_kernel_f32.  Same flat order, same keys, same fp64
+// mean / std / theta; a parameter lives at a FLOAT offset, matrices with the rows of two consecutive units interleaved:
+//     W (l, r, k) at  HDR + offW[l] + ((r / 2) ld[l] + k) 2 + (r & 1),   b (l, r) at  HDR + offb[l] + r      (HDR in floats)
+// and is stored with one round-to-nearest conversion of the fp64 value the fp64 kernel would store (sample: the sum formed
+// in fp64 first, so a float32 member is (float) of the fp64 population's under the same keys); get widens exactly.  The
+// noise sum does not read the blocks: one kernel serves both kinds.
 #pragma once
 
 namespace pcg {
@@ -39,10 +47,11 @@ constexpr int POP_CHUNK = 64;            // members per partial sum of pcg_polic
 constexpr int POP_BLOCK = 256;
 constexpr int POP_MAX_GRID_Y = 32768;    // rows of the grid; the kernels stride over members / chunks / rows beyond it
 
-// Where the flat parameters of a member live in its device block (offsets in doubles from the block's first byte, the header
-// included): a few words that travel in the kernel arguments.
+// Where the flat parameters of a member live in its device block (offsets in ELEMENTS from the block's first byte, the header
+// included -- doubles, or floats for a float32 population): a few words that travel in the kernel arguments.
 struct PopLayout {
   int32_t n;         // parameters per member
+  int32_t f32;       // element kind: 0 doubles, rows plain; 1 floats, the rows of two consecutive units interleaved
   int32_t nl;        // layers (1..3)
   int32_t start[4];  // flat index of layer l's first parameter; start[nl] = n
   int32_t rows[3], cols[3], ld[3], offW[3], offb[3];
@@ -61,6 +70,19 @@ __device__ __forceinline__ int pop_param_offset(const PopLayout& L, int j) {
   return L.offW[l] + r * L.ld[l] + (local - r * cols);
 }
 
+// ... of a float32 population: offset in floats, pack_policy_f32's interleaved rows
+__device__ __forceinline__ int pop_param_offset_f32(const PopLayout& L, int j) {
+  int l = 0;
+  if (L.nl > 1 && j >= L.start[1]) l = 1;
+  if (L.nl > 2 && j >= L.start[2]) l = 2;
+  const int local = j - L.start[l];
+  const int cols = L.cols[l];
+  const int nw = L.rows[l] * cols;
+  if (local >= nw) return L.offb[l] + (local - nw);
+  const int r = local / cols;
+  return L.offW[l] + ((r >> 1) * L.ld[l] + (local - r * cols)) * 2 + (r & 1);
+}
+
 // the four variates of block b for stream q (the float results of the two Box-Muller pairs)
 __device__ __forceinline__ void pop_noise4(uint32_t q, uint32_t b, uint32_t g, uint32_t k0, uint32_t k1, float (&z)[4]) {
   uint32_t o[4];
@@ -71,8 +93,8 @@ __device__ __forceinline__ void pop_noise4(uint32_t q, uint32_t b, uint32_t g, u
 
 struct PopSampleArgs {
   PopLayout L;
-  double* blocks;   // member 0's block
-  int64_t stride;   // doubles between two members' blocks
+  double* blocks;   // member 0's block (floats behind it when L.f32)
+  int64_t stride;   // elements (doubles, or floats when L.f32) between two members' blocks
   int32_t first, count, antithetic;
   uint32_t k0, k1, g;
   const double* mean;
@@ -105,6 +127,39 @@ __global__ __launch_bounds__(POP_BLOCK) void pop_sample_kernel(const PopSampleAr
         const double zz = neg ? -(double)z[k] : (double)z[k];
         const double pr = sd[k] * zz;
         blk[off[k]] = mu[k] + pr;
+      }
+    }
+  }
+}
+
+// the float32 sibling: the same fp64 sum, stored with one round-to-nearest conversion (an overflow is stored as +-inf)
+__global__ __launch_bounds__(POP_BLOCK) void pop_sample_kernel_f32(const PopSampleArgs A) {
+  const int b = (int)(blockIdx.x * POP_BLOCK + threadIdx.x);
+  const int j0 = 4 * b;
+  if (j0 >= A.L.n) return;
+  double mu[4], sd[4];
+  int off[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bool in = j0 + i < A.L.n;
+    mu[i] = in ? A.mean[j0 + i] : 0.0;
+    sd[i] = in ? A.std[j0 + i] : 0.0;
+    off[i] = in ? pop_param_offset_f32(A.L, j0 + i) : 0;
+  }
+  for (int64_t i = blockIdx.y; i < A.count; i += gridDim.y) {
+    const uint32_t m = (uint32_t)(A.first + i);
+    float z[4];
+    pop_noise4(A.antithetic ? m >> 1 : m, (uint32_t)b, A.g, A.k0, A.k1, z);
+    const bool neg = A.antithetic && (m & 1u);
+    float* blk = reinterpret_cast<float*>(A.blocks) + (int64_t)m * A.stride;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (j0 + k < A.L.n) {
+#pragma clang fp contract(off)
+        const double zz = neg ? -(double)z[k] : (double)z[k];
+        const double pr = sd[k] * zz;
+        const double th = mu[k] + pr;
+        blk[off[k]] = (float)th;
       }
     }
   }
@@ -166,8 +221,8 @@ __global__ __launch_bounds__(POP_BLOCK) void pop_chunk_sum_kernel(const PopDotAr
 
 struct PopFlatArgs {
   PopLayout L;
-  double* blocks;
-  int64_t stride;          // doubles between two members' blocks
+  double* blocks;          // (floats behind it when L.f32)
+  int64_t stride;          // elements (doubles, or floats when L.f32) between two members' blocks
   int32_t P, first, count;
   const int32_t* members;  // get: [count] member indices (device), or null for first + i
   double* theta;           // [count][theta_stride]
@@ -192,6 +247,30 @@ __global__ __launch_bounds__(POP_BLOCK) void pop_set_flat_kernel(const PopFlatAr
   for (int64_t i = blockIdx.y; i < A.count; i += gridDim.y) {
     const int64_t m = (int64_t)A.first + i;  // (inside [0, P): checked on the host)
     A.blocks[m * A.stride + off] = A.theta[i * A.theta_stride + j];
+  }
+}
+
+// the float32 siblings: the stored float widened exactly / theta rounded to nearest
+__global__ __launch_bounds__(POP_BLOCK) void pop_get_flat_kernel_f32(const PopFlatArgs A) {
+  const int j = (int)(blockIdx.x * POP_BLOCK + threadIdx.x);
+  if (j >= A.L.n) return;
+  const int off = pop_param_offset_f32(A.L, j);
+  const float* blocks = reinterpret_cast<const float*>(A.blocks);
+  for (int64_t i = blockIdx.y; i < A.count; i += gridDim.y) {
+    const int64_t m = A.members ? (int64_t)A.members[i] : (int64_t)A.first + i;
+    const bool ok = m >= 0 && m < A.P;
+    A.theta[i * A.theta_stride + j] = ok ? (double)blocks[m * A.stride + off] : __builtin_nan("");
+  }
+}
+
+__global__ __launch_bounds__(POP_BLOCK) void pop_set_flat_kernel_f32(const PopFlatArgs A) {
+  const int j = (int)(blockIdx.x * POP_BLOCK + threadIdx.x);
+  if (j >= A.L.n) return;
+  const int off = pop_param_offset_f32(A.L, j);
+  float* blocks = reinterpret_cast<float*>(A.blocks);
+  for (int64_t i = blockIdx.y; i < A.count; i += gridDim.y) {
+    const int64_t m = (int64_t)A.first + i;  // (inside [0, P): checked on the host)
+    blocks[m * A.stride + off] = (float)A.theta[i * A.theta_stride + j];
   }
 }
 

@@ -18,8 +18,11 @@
 //            nor re-reads T x B rewards:   J = J + disc * r;  disc = disc * gamma   from J = 0, disc = 1, every operation
 //            rounded on its own (contraction off for the two statements, as in pcg_gae.hpp).  That defines the bits.
 //
-// Out of scope: stochastic actors over a population, float32 members, plans with constraint rows, with per-env parameters and
-// with run-time compiled code (whose module does not carry this kernel: ahead-of-time only).
+// A float32 population (pcg_policy_pop_create_f32) is P blocks of pack_policy_f32's form, and rollout_pop_policy_kernel_f32
+// below is the same loop with pcg_rollout_policy_f32.hpp's evaluator: the network in float32, the env, J and disc in fp64.
+//
+// Out of scope: stochastic actors over a population, plans with constraint rows, with per-env parameters and with run-time
+// compiled code (whose module does not carry these kernels: ahead-of-time only).
 #pragma once
 
 namespace pcg {
@@ -67,6 +70,69 @@ __global__ __launch_bounds__(BLOCK, M::NX <= 10 ? PCG_POL_WPE : 1) void rollout_
   const int n_eval = A.T + ((Q.record_next && Q.a_out) ? 1 : 0);
   for (int s = 0; s < n_eval; ++s) {
     policy_eval<NIN, NA>(P, in, a);
+    if (Q.a_out) {
+      double* ao = Q.a_out + (size_t)s * Q.ao_ss + e;
+#pragma unroll
+      for (int i = 0; i < NA; ++i)
+        if (i < na) ao[(size_t)i * Q.ao_cs] = a[i];
+    }
+    if (s == A.T) break;  // row T: policy(observation after the last step), recorded and not applied
+    const bool last = (s == A.T - 1);
+    EnvOut<M> out;
+    env_step<M, INTEG, false, false, true>(A, c, nullptr, nullptr, e, A.t_scalar + s, a, x, out);
+    {
+#pragma clang fp contract(off)
+      const double dr = disc * out.rew;
+      J = J + dr;
+      disc = disc * Q.gamma;
+    }
+    disc = pop_uniform(disc);
+    if (A.rew_seq) A.rew_seq[(size_t)s * A.r_ss + e] = out.rew;
+    if (A.obs_seq) store_obs<M>(A, c, out, A.obs_seq + (size_t)s * A.o_ss + e, A.o_cs);
+    if (last) store_out<M>(A, c, e, out, A.obs + e);  // io->obs/rew/done hold the last step
+    else if (A.status && out.status != PCG_ST_OK) A.status[e] = out.status;
+    policy_input<M, NIN>(c, out, in);
+  }
+  if (Q.ret_out) Q.ret_out[e] = J;
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+    if (i < nx) A.x[(size_t)i * B + e] = x[i];
+}
+
+// The same loop with the member's network evaluated in float32: policy_raw_f32 + policy_map_f32 (pcg_rollout_policy_f32.hpp)
+// in place of policy_eval, on a block of pack_policy_f32's form.  A float32 block is half the bytes a wave streams per step.
+// Waves per SIMD asked for the models of up to ten states: rollout_policy_kernel_f32's two, for the reason given above that
+// kernel -- the bitwise replay of the recorded actions through the open-loop general kernel is the bar
+// (tests/test_gpu_pop_f32.py), and a register budget is changed HERE when an instantiation misses it.
+#ifndef PCG_POP32_WPE
+#define PCG_POP32_WPE PCG_POL32_WPE
+#endif
+template <class M, int INTEG>
+__global__ __launch_bounds__(BLOCK, M::NX <= 10 ? PCG_POP32_WPE : 1) void rollout_pop_policy_kernel_f32(const StepArgs A, const PopArgs Q) {
+  CDevConst& c = *A.C;
+  constexpr int NX = M::NX, NA = M::NA, NIN = policy_nin<M>();
+  const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= A.B) return;
+  // (the same value in every lane of the wave, as in rollout_pop_policy_kernel)
+  const int m = __builtin_amdgcn_readfirstlane((int)((A.env_offset + e) / Q.G));
+  const PCG_CONSTANT PolicyDev& P = *reinterpret_cast<const PCG_CONSTANT PolicyDev*>(Q.blocks + (int64_t)m * Q.stride);
+  const int64_t B = A.B;
+  const int nx = M::DYNAMIC ? c.nx : NX;
+  const int na = M::DYNAMIC ? c.na : NA;
+  const int nobs = c.nobs;
+  double x[NX], a[NA], in[NIN];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) x[i] = (i < nx) ? A.x[(size_t)i * B + e] : 0.0;
+#pragma unroll
+  for (int i = 0; i < NIN; ++i) in[i] = (i < nobs) ? A.obs[(size_t)i * B + e] : 0.0;
+  double J = 0.0, disc = 1.0;
+  const int n_eval = A.T + ((Q.record_next && Q.a_out) ? 1 : 0);
+  for (int s = 0; s < n_eval; ++s) {
+    {
+      float raw[NA];
+      policy_raw_f32<NIN, NA>(P, in, raw);
+      policy_map_f32<NA>(P, raw, a);
+    }
     if (Q.a_out) {
       double* ao = Q.a_out + (size_t)s * Q.ao_ss + e;
 #pragma unroll

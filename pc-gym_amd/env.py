@@ -448,7 +448,8 @@ class VecEnv:
                            collect_returns=True, record_next_action=False):
         """``rollout_policy`` with a :class:`~pcgym_amd.policy.PolicyPopulation`: T steps in one launch
         (``pcg_rollout_policy_pop``), env ``e`` driven by member ``(env_offset + e) // envs_per_policy`` -- each env computes
-        what ``rollout_policy`` with that member computes, bit for bit.  Returns a dict: "a" (T [+1], na, B), "obs"
+        what ``rollout_policy`` with that member computes, bit for bit (a float32 population: with its float32 member, the
+        network evaluated in float32 inside the kernel).  Returns a dict: "a" (T [+1], na, B), "obs"
         (T, Nobs, B), "rew" (T, B), "ret" (B,) -- None where not asked for.  "ret" is each env's discounted return of THIS
         call's steps (``J = J + disc * rew; disc = disc * gamma`` from J = 0, disc = 1, each operation rounded on its own),
         accumulated in the kernel: a search loop needs no T x B rewards.  ``envs_per_policy`` and the env offset must be

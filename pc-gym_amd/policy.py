@@ -252,30 +252,38 @@ def fused_unc_ok(spec, policy):
 
 
 class PolicyPopulation:
-    """P float64 :class:`MLPPolicy` networks of ONE shape, each driving its own slice of a batch: what derivative-free policy
-    search over the weights, the comparison of a set of checkpoints and hyper-parameter sweeps roll -- in ONE launch
+    """P :class:`MLPPolicy` networks of ONE shape and dtype, each driving its own slice of a batch: what derivative-free
+    policy search over the weights, the comparison of a set of checkpoints and hyper-parameter sweeps roll -- in ONE launch
     (``pcg_rollout_policy_pop``, ``VecEnv.rollout_population``) instead of P launches of a few workgroups.
 
     weights[l] : (P, n_next, n_prev) array, biases[l] : (P, n_next); activation, out_map and the clip box are shared.
+    dtype : "float64" (default) | "float32", as :class:`MLPPolicy`'s: under "float32" weights, biases and the clip box are
+    stored as ``np.float32`` (rounded to nearest; an overflow raises ValueError), the callable computes in torch float32 on
+    ``obs.to(float32)`` and returns float64 tensors, and the device form is ``pcg_policy_pop_create_f32``: every member is
+    evaluated in float32 inside the kernel, as stable-baselines3 evaluates the checkpoints it trained.
     Env ``e`` of a batch is driven by member ``(env_offset + e) // envs_per_policy`` (the global env index: a sharded batch
     splits a population the way it splits the random streams).
 
     The weights can also be written and read ON the device, in the flat parameter order of :meth:`flat_layout`
     (include/pcgym_hip.h, csrc/pcg_pop_search.hpp): :meth:`sample_` draws members of a diagonal Gaussian straight into the
     packed blocks, :meth:`noise_dot` forms an evolution strategy's score-weighted noise sum from the same keys,
-    :meth:`flat` / :meth:`set_flat_` move flat parameter vectors out and in.  After a device-side write the host arrays
+    :meth:`flat` / :meth:`set_flat_` move flat parameter vectors out and in -- float64 tensors for either dtype: a float32
+    population stores each value with one round-to-nearest conversion and hands it back widened exactly.  After a device-side write the host arrays
     ``weights`` / ``biases`` are stale for those members; everything that reads them (``member``, the callable, ``to_cfg``,
     ``update_``, ``close``) first brings them back with one :meth:`flat` and one copy.  A population never written from the
     device behaves as it always did."""
 
-    def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0):
+    def __init__(self, weights, biases, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype="float64"):
+        if dtype not in _DTYPE:
+            raise ValueError(f"dtype must be one of {sorted(_DTYPE)}, not {dtype!r}")
+        self.dtype = dtype
         if activation not in _ACT:
             raise ValueError(f"activation must be one of {sorted(_ACT)}, not {activation!r}")
         if out_map not in _OUT:
             raise ValueError(f"out_map must be one of {sorted(_OUT)}, not {out_map!r}")
-        self.weights, self.biases = self._arrays(weights, biases)
+        self.weights, self.biases = self._arrays(weights, biases, _DTYPE[dtype])
         self.activation, self.out_map = activation, out_map
-        self.out_low, self.out_high = float(out_low), float(out_high)
+        self.out_low, self.out_high = float(_as(out_low, _DTYPE[dtype], "out_low")), float(_as(out_high, _DTYPE[dtype], "out_high"))
         self.P = int(self.weights[0].shape[0])
         self.n_in, self.n_out = int(self.weights[0].shape[2]), int(self.weights[-1].shape[1])
         self.n_hidden = len(self.weights) - 1
@@ -286,10 +294,11 @@ class PolicyPopulation:
         self._stale_dev = None  # index of the device that holds them
 
     @staticmethod
-    def _arrays(weights, biases):
-        """contiguous float64 (P, n_next, n_prev) / (P, n_next) arrays of one member count whose layers chain, or ValueError"""
-        ws = [np.ascontiguousarray(np.asarray(w, dtype=np.float64)) for w in weights]
-        bs = [np.ascontiguousarray(np.asarray(b, dtype=np.float64)) for b in biases]
+    def _arrays(weights, biases, np_dtype=np.float64):
+        """contiguous (P, n_next, n_prev) / (P, n_next) arrays of `np_dtype` (rounded to nearest; a float32 overflow raises) of
+        one member count whose layers chain, or ValueError"""
+        ws = [np.ascontiguousarray(_as(w, np_dtype, "weights")) for w in weights]
+        bs = [np.ascontiguousarray(_as(b, np_dtype, "biases")) for b in biases]
         if not ws or len(ws) != len(bs):
             raise ValueError("one bias array per weight array, at least one layer")
         if ws[0].ndim != 3 or ws[0].shape[0] < 1:
@@ -304,35 +313,38 @@ class PolicyPopulation:
 
     @classmethod
     def from_policies(cls, policies):
-        """From float64 MLPPolicy objects of one shape, activation, output map and clip box (ValueError otherwise)"""
+        """From MLPPolicy objects of one dtype (all float64 or all float32), shape, activation, output map and clip box
+        (ValueError otherwise); the population has the members' dtype"""
         policies = list(policies)
         if not policies:
             raise ValueError("from_policies needs at least one policy")
         p0 = policies[0]
         for p in policies:
-            if not isinstance(p, MLPPolicy) or p.dtype != "float64":
-                raise ValueError("from_policies takes float64 MLPPolicy objects")
+            if not isinstance(p, MLPPolicy) or not isinstance(p0, MLPPolicy) or p.dtype != p0.dtype:
+                raise ValueError("from_policies takes MLPPolicy objects of one dtype: all float64 or all float32")
             if ([w.shape for w in p.weights] != [w.shape for w in p0.weights]
                     or (p.activation, p.out_map, p.out_low, p.out_high) != (p0.activation, p0.out_map, p0.out_low, p0.out_high)):
                 raise ValueError("the members of a population share shape, activation, output map and clip box")
         return cls([np.stack([p.weights[l] for p in policies]) for l in range(len(p0.weights))],
                    [np.stack([p.biases[l] for p in policies]) for l in range(len(p0.biases))],
-                   activation=p0.activation, out_map=p0.out_map, out_low=p0.out_low, out_high=p0.out_high)
+                   activation=p0.activation, out_map=p0.out_map, out_low=p0.out_low, out_high=p0.out_high, dtype=p0.dtype)
 
     def member(self, i):
-        """member ``i`` as an MLPPolicy of its own (copies of the weights)"""
+        """member ``i`` as an MLPPolicy of its own, of the population's dtype (copies of the weights)"""
         i = int(i)
         if not 0 <= i < self.P:
             raise ValueError(f"member {i} of a population of {self.P}")
         self._refresh()
         return MLPPolicy([w[i].copy() for w in self.weights], [b[i].copy() for b in self.biases], activation=self.activation,
-                         out_map=self.out_map, out_low=self.out_low, out_high=self.out_high)
+                         out_map=self.out_map, out_low=self.out_low, out_high=self.out_high, dtype=self.dtype)
 
-    # ---- the callable: torch fp64 on the observation's device, each slice with its member ----------------------------------
+    # ---- the callable: torch fp64 (float32 for a float32 population) on the observation's device, each slice with its member
     def __call__(self, obs, envs_per_policy, env_offset=0):
         """obs (B, Nobs) -> (B, na): rows ``e`` with ``(env_offset + e) // envs_per_policy == m`` through member ``m``,
         in MLPPolicy's arithmetic: one ``addmm`` per layer and member present -- on CPU tensors the bits of the member's own
-        ``MLPPolicy.__call__`` on its slice -- or, for whole slices on a GPU, one ``baddbmm`` per layer over all members"""
+        ``MLPPolicy.__call__`` on its slice -- or, for whole slices on a GPU, one ``baddbmm`` per layer over all members.
+        A float32 population computes in torch float32 on ``obs.to(float32)`` in both forms, applies a ``tanh`` output map in
+        float32 and returns float64 tensors (exact widening)."""
         torch = _torch()
         obs = torch.as_tensor(obs)
         G, off, B = int(envs_per_policy), int(env_offset), int(obs.shape[0])
@@ -346,45 +358,45 @@ class PolicyPopulation:
             self._tensors[key] = ([torch.as_tensor(w, device=obs.device) for w in self.weights],
                                   [torch.as_tensor(b, device=obs.device) for b in self.biases])
         Ws, bs = self._tensors[key]
+        f32 = self.dtype == "float32"
+        tdt = torch.float32 if f32 else torch.float64
+
+        def out_map(h):
+            if self.out_map == "tanh":
+                return torch.tanh(h).to(torch.float64)  # (in the network's dtype, before the widening: as in the kernel)
+            h = h.to(torch.float64)
+            return torch.clamp(h, self.out_low, self.out_high) if self.out_map == "clip" else h
+
         if obs.is_cuda and B and off % G == 0 and B % G == 0:
             # whole slices on a GPU: one batched product per layer over the members present
             m0, n = off // G, B // G
-            h = obs.to(torch.float64).reshape(n, G, self.n_in)
+            h = obs.to(tdt).reshape(n, G, self.n_in)
             for l in range(self.n_hidden + 1):
                 h = torch.baddbmm(bs[l][m0:m0 + n].unsqueeze(1), h, Ws[l][m0:m0 + n].transpose(1, 2))
                 if l < self.n_hidden:
                     h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
-            h = h.reshape(B, self.n_out)
-            if self.out_map == "clip":
-                h = torch.clamp(h, self.out_low, self.out_high)
-            elif self.out_map == "tanh":
-                h = torch.tanh(h)
-            return h
+            return out_map(h.reshape(B, self.n_out))
         out = torch.empty((B, self.n_out), dtype=torch.float64, device=obs.device)
         e = 0
         while e < B:
             m = (off + e) // G
             e1 = min(B, (m + 1) * G - off)
-            h = obs[e:e1].to(torch.float64)
+            h = obs[e:e1].to(tdt)
             for l in range(self.n_hidden + 1):
                 h = torch.addmm(bs[l][m], h, Ws[l][m].t())
                 if l < self.n_hidden:
                     h = torch.tanh(h) if self.activation == "tanh" else torch.relu(h)
-            if self.out_map == "clip":
-                h = torch.clamp(h, self.out_low, self.out_high)
-            elif self.out_map == "tanh":
-                h = torch.tanh(h)
-            out[e:e1] = h
+            out[e:e1] = out_map(h)
             e = e1
         return out
 
     def update_(self, weights, biases, first=0):
         """New weights for members ``first .. first + count - 1`` (``count`` = the arrays' leading size), in place: host
         arrays, cached torch tensors and every live device handle (``pcg_policy_pop_update``: the device blocks are
-        rewritten, nothing is allocated or freed).  Another shape or a range outside the population raises ValueError and
-        leaves the population as it was."""
+        rewritten, nothing is allocated or freed).  A float32 population rounds first.  Another shape, a range outside the
+        population or a value that overflows float32 raises ValueError and leaves the population as it was, host and device."""
         self._refresh()
-        ws, bs = self._arrays(weights, biases)
+        ws, bs = self._arrays(weights, biases, _DTYPE[self.dtype])
         first, count = int(first), int(ws[0].shape[0])
         if ([w.shape[1:] for w in ws] != [w.shape[1:] for w in self.weights] or first < 0 or first + count > self.P):
             raise ValueError(f"update_ keeps the shape {[w.shape[1:] for w in self.weights]} and stays inside the {self.P} members: "
@@ -412,19 +424,23 @@ class PolicyPopulation:
         cfg.activation, cfg.out_map = _ACT[self.activation], _OUT[self.out_map]
         cfg.out_low, cfg.out_high = self.out_low, self.out_high
         pd = C.POINTER(C.c_double)
-        ws, bs = [np.ascontiguousarray(w) for w in ws], [np.ascontiguousarray(b) for b in bs]
+        # (pcg_policy_cfg carries doubles: a float32 population passes exact widenings, which the float32 device form rounds back)
+        ws = [np.ascontiguousarray(w, dtype=np.float64) for w in ws]
+        bs = [np.ascontiguousarray(b, dtype=np.float64) for b in bs]
         for l in range(min(len(ws), 3)):
             cfg.W[l] = ws[l].ctypes.data_as(pd)
             cfg.b[l] = bs[l].ctypes.data_as(pd)
         return cfg, [ws, bs]
 
     def to_cfg(self):
-        """(pcg_policy_cfg with member-major arrays, keep-alive list): what ``pcg_policy_pop_create`` takes beside ``P``"""
+        """(pcg_policy_cfg with member-major float64 arrays, keep-alive list): what ``pcg_policy_pop_create`` /
+        ``pcg_policy_pop_create_f32`` take beside ``P``"""
         self._refresh()
         return self._cfg(self.weights, self.biases)
 
     def validate(self):
         """0 when the device form can hold every member (host only), else the first failing status of pcg_policy_validate.
+        (A float32 population's host arrays are float32 values already: what is finite there fits the float32 device form.)
         Remembered: a device-side write keeps the shape, and the values it writes are not inspected (include/pcgym_hip.h says
         what a rollout does with a non-finite member), so it leaves a remembered 0 standing and a search loop reads nothing
         back between generations."""
@@ -449,7 +465,8 @@ class PolicyPopulation:
             cfg, keep = self.to_cfg()
             h = C.c_void_p()
             with torch.cuda.device(idx):
-                _lib.check(_lib.load().pcg_policy_pop_create(C.byref(h), C.byref(cfg), self.P), "pcg_policy_pop_create")
+                create = "pcg_policy_pop_create_f32" if self.dtype == "float32" else "pcg_policy_pop_create"
+                _lib.check(getattr(_lib.load(), create)(C.byref(h), C.byref(cfg), self.P), create)
             self._handles[idx] = h
         return self._handles[idx]
 
@@ -559,6 +576,7 @@ class PolicyPopulation:
             theta = self._flat(idx, members, 0, int(which.size))
         theta = theta.cpu().numpy()
         for name, l, a, b, shape in self.flat_layout():
+            # (a float32 population's flat() holds float32 values: the assignment narrows them exactly)
             (self.weights if name == "W" else self.biases)[l][which] = theta[:, a:b].reshape((-1,) + shape)
         self._stale[:] = False
         self._tensors = {}
@@ -567,7 +585,9 @@ class PolicyPopulation:
         """Members ``first .. first + count - 1`` drawn from the diagonal Gaussian N(mean, diag(std^2)) straight into the packed
         device blocks (``pcg_policy_pop_sample``): ``theta[m, j] = mean[j] + std[j] * z(m, j)`` with the search noise of the
         RNG contract (keyed by ``seed``, ``generation``, the member and the parameter), ``antithetic``: members
-        ``2q`` and ``2q + 1`` get ``+z`` and ``-z``.  Nothing crosses to the host and no other member is touched.
+        ``2q`` and ``2q + 1`` get ``+z`` and ``-z``.  Nothing crosses to the host and no other member is touched.  A float32
+        population forms the same float64 sum and stores it with one round-to-nearest conversion: bit for bit ``float32`` of
+        what a float64 population holds under the same arguments (an overflow is stored as an infinity, not inspected).
 
         mean, std : float64 tensors of shape ``(n_params,)`` on the population's device (numpy arrays are copied there).
         check     : True costs one reduction and one synchronisation and raises ValueError unless ``mean`` is finite and
@@ -596,7 +616,8 @@ class PolicyPopulation:
         ``first .. first + len(weights) - 1``, formed from the keys :meth:`sample_` drew with -- the noise is never stored
         (``pcg_policy_pop_noise_dot``: a fixed summation order in chunks of 64 members, the same bits for every launch).
         weights : (count,) float64 tensor on the population's device (numpy arrays are copied).  Returns an ``(n_params,)``
-        device tensor; the workspace is allocated by torch here."""
+        device tensor; the workspace is allocated by torch here.  The blocks are not read: on a float32 population a member's
+        realised perturbation is ``round32(mean + std z) - mean``, the sum uses the unrounded ``z`` (ordinary ES noise)."""
         torch = _torch()
         idx = self._search_device()
         w = self._as_device(weights, idx, torch.float64, None, "weights")
@@ -620,7 +641,8 @@ class PolicyPopulation:
     def flat(self, members=None, first=0, count=None):
         """(count, n_params) float64 device tensor of flat parameter vectors (:meth:`flat_layout`'s order), read from the
         packed device blocks (``pcg_policy_pop_get_flat``): members ``first .. first + count - 1``, or the rows ``members``
-        names (a sequence or an int32 / int64 tensor; repeats allowed; an index outside ``[0, P)`` gives a row of NaN)."""
+        names (a sequence or an int32 / int64 tensor; repeats allowed; an index outside ``[0, P)`` gives a row of NaN).  A
+        float32 population's rows hold its float32 values exactly."""
         torch = _torch()
         idx = self._search_device()
         dev = torch.device("cuda", idx)
@@ -639,7 +661,7 @@ class PolicyPopulation:
     def set_flat_(self, theta, first=0):
         """Members ``first .. first + count - 1`` from the rows of ``theta`` (count, n_params), float64 on the population's
         device (numpy arrays are copied there): the device-to-device form of :meth:`update_` (``pcg_policy_pop_set_flat``).
-        The values are not inspected."""
+        The values are not inspected; a float32 population stores ``float32(theta)``, rounded to nearest."""
         torch = _torch()
         idx = self._search_device(write=True)
         t = self._as_device(theta, idx, torch.float64, None, "theta")
@@ -663,8 +685,8 @@ class PolicyPopulation:
 def fused_pop_ok(spec, pop, envs_per_policy):
     """the plans, populations and slices pcg_rollout_policy_pop takes (include/pcgym_hip.h): a built-in plan (no user model,
     no reward or constraint expression: the run-time compiled module does not carry the population kernel), fixed-step
-    RK4 / CV8, no constraint rows, no per-env parameters; members of the plan's sizes that the device form can hold; slices
-    of whole waves (a multiple of 64 envs)"""
+    RK4 / CV8, no constraint rows, no per-env parameters; members of the plan's sizes that the device form can hold, float64
+    or float32; slices of whole waves (a multiple of 64 envs)"""
     G = int(envs_per_policy)
     return (isinstance(pop, PolicyPopulation) and spec.integrator in ("rk4", "cv8") and not spec.ncon and not spec.nunc
             and not _runtime_compiled(spec) and G >= 64 and G % 64 == 0

@@ -198,7 +198,8 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
     Route: ONE launch (``pcg_rollout_policy_pop``, the returns accumulated in the kernel) when ``fused_pop_ok`` and the env
     offset is a multiple of 64; otherwise -- or with ``fused=False`` -- one ``env.step`` per step with the population's
     callable form and the kernel's recurrence in torch (``J = J + disc * rew; disc = disc * gamma``).  ``fused=True`` raises
-    ValueError where the one launch is not possible."""
+    ValueError where the one launch is not possible.  A float32 population takes the same routes: the float32 kernel, or the
+    float32 callable per step."""
     torch = _torch()
     s = env.spec
     B, G, off = env.B, int(envs_per_policy), int(env.env_offset)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A population of MLP policies in one fused closed-loop launch (pcg_rollout_policy_pop) against what a caller had before it.
 
-    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--out FILE]
+    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--dtype float32] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s; one episode = 59 closed-loop steps).  All
 routes of a comparison alternate inside one process (`reps` rounds after one warm-up round); times are device-event times
@@ -17,6 +17,12 @@ is the median, the repeats are printed.
          step  evaluate_population(fused=False): one env.step per step with the population's callable form in torch
   3  benefit of ret_out         the population call returning ret_out alone against recording rew (T x B) and reducing it
                                 in torch with the same discounting
+  4  float32 members            (the default part under --dtype float32) P in {16, 256, 4096} distinct members on B / P envs each,
+                                and 64 envs per member with the last shape: the float32 population, the fp64 population on the
+                                same rounded weights, and rollout_policy with ONE float32 policy on the same envs (nothing
+                                recorded anywhere)
+
+--dtype float32 makes the populations and policies of parts 1 to 3 float32 ones as well.
 """
 import argparse
 import os
@@ -67,12 +73,12 @@ def part1(a, p, torch, VecEnv, PolicyPopulation, MLPPolicy):
         env = VecEnv(dict(p), n_envs=a.B, seed=1)
         spec, T = env.spec, env.spec.N - 1
         Ws, bs = member_arrays(spec, SHAPES[name], 1)
-        pol = MLPPolicy([w[0] for w in Ws], [b[0] for b in bs], activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+        pol = MLPPolicy([w[0] for w in Ws], [b[0] for b in bs], activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
         pops = {}
         for G in (1 << 14, 1024, 64):
             P = (a.B + G - 1) // G
             pops[G] = PolicyPopulation([np.broadcast_to(w, (P,) + w.shape[1:]) for w in Ws], [np.broadcast_to(b, (P,) + b.shape[1:]) for b in bs],
-                                       activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+                                       activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
             pops[G].handle(env.device)
         x0, o0 = None, None
         env.reset()
@@ -119,7 +125,7 @@ def part2(a, p, torch, VecEnv, PolicyPopulation, evaluate_population):
             big, big2, small = VecEnv(dict(p), n_envs=a.B, seed=1), VecEnv(dict(p), n_envs=a.B, seed=1), VecEnv(dict(p), n_envs=G, seed=1)
             spec, T = big.spec, big.spec.N - 1
             Ws, bs = member_arrays(spec, SHAPES[name], P)
-            pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+            pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
             pop.handle(big.device)
             members = [pop.member(m) for m in range(P)]
             for q in members:
@@ -162,7 +168,7 @@ def part3(a, p, torch, VecEnv, PolicyPopulation):
     env = VecEnv(dict(p), n_envs=a.B, seed=1)
     spec, T, G = env.spec, env.spec.N - 1, 1024
     Ws, bs = member_arrays(spec, SHAPES["1x16"], (a.B + G - 1) // G)
-    pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+    pop = PolicyPopulation(Ws, bs, activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
     pop.handle(env.device)
     env.reset()
     x0, o0 = env.x.clone(), env.obs_soa.clone()
@@ -191,12 +197,62 @@ def part3(a, p, torch, VecEnv, PolicyPopulation):
     return lines
 
 
+def part4(a, p, torch, VecEnv, PolicyPopulation, MLPPolicy):
+    lines = ["# 4. float32 members, ms per episode of B envs (nothing recorded): f32 = the float32 population, f64 = the fp64 population "
+             "on the same rounded weights, one32 = rollout_policy with ONE float32 policy (member 0) on the same envs"]
+    names = a.shapes.split(",")
+    cases = [(name, a.B // P) for name in names for P in (16, 256, 4096)] + [(names[-1], 64)]
+    for name, G in cases:
+        if G < 64 or G % 64:
+            continue
+        P = (a.B + G - 1) // G
+        env = VecEnv(dict(p), n_envs=a.B, seed=1)
+        T = env.spec.N - 1
+        Ws, bs = member_arrays(env.spec, SHAPES[name], P)
+        kw = dict(activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+        pop32 = PolicyPopulation(Ws, bs, dtype="float32", **kw)
+        pop64 = PolicyPopulation([w.astype(np.float64) for w in pop32.weights], [b.astype(np.float64) for b in pop32.biases], **kw)
+        one32 = pop32.member(0)
+        for q in (pop32, pop64, one32):
+            q.handle(env.device)
+        env.reset()
+        x0, o0 = env.x.clone(), env.obs_soa.clone()
+
+        def restart():
+            env.x.copy_(x0), env.obs_soa.copy_(o0)
+            env.t = 0
+
+        def with_pop(q):
+            def run():
+                restart()
+                env.rollout_population(q, T, G, collect_returns=False)
+            return run
+
+        def single():
+            restart()
+            env.rollout_policy(one32, T, collect_rew=False, collect_actions=False)
+
+        times = timed(torch, {"f32": with_pop(pop32), "f64": with_pop(pop64), "one32": single}, a.reps)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        lines.append(f"{name:7s} P={P:6d} G={G:6d}   f32 {med['f32']:8.3f}   f64 {med['f64']:8.3f}   one32 {med['one32']:8.3f} ms   "
+                     f"f64 / f32 = {med['f64'] / med['f32']:.2f}   f32 / one32 = {med['f32'] / med['one32']:.3f}   "
+                     f"({med['f32'] / T * 1e3:.1f} / {med['f64'] / T * 1e3:.1f} / {med['one32'] / T * 1e3:.1f} us per step)")
+        lines.append("        repeats " + fmt(times))
+        env.close()
+        for q in (pop32, pop64, one32):
+            q.close()
+        del env, pop32, pop64, one32
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="affine,1x16,2x64")
-    ap.add_argument("--parts", default="1,2,3")
+    ap.add_argument("--parts", help="default: 1,2,3; under --dtype float32: 4")
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -206,11 +262,11 @@ def main():
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lib = _lib.load()
-    lines = [f"# tools/population_rollout_bench.py  B={a.B} reps={a.reps}  library build {lib.pcg_build_id().decode()} "
+    lines = [f"# tools/population_rollout_bench.py  B={a.B} reps={a.reps} dtype={a.dtype}  library build {lib.pcg_build_id().decode()} "
              f"({os.path.relpath(_lib.LIB_PATH, ROOT)}, {os.path.getsize(_lib.LIB_PATH)} bytes)  {torch.cuda.get_device_name(0)}",
              "# cstr, RK4 x 1, N = 60: one episode = 59 closed-loop steps; median of the interleaved repeats"]
     p = bench.workload_params()
-    parts = a.parts.split(",")
+    parts = (a.parts or ("4" if a.dtype == "float32" else "1,2,3")).split(",")
 
     def flush():
         text = "\n".join(lines)
@@ -227,6 +283,9 @@ def main():
         flush()
     if "3" in parts:
         lines += part3(a, p, torch, VecEnv, PolicyPopulation)
+        flush()
+    if "4" in parts:
+        lines += part4(a, p, torch, VecEnv, PolicyPopulation, MLPPolicy)
         flush()
     print("\n".join(lines))
 

@@ -2,7 +2,7 @@
 """One generation of a policy search around pcg_rollout_policy_pop: the weights born and refitted on the host (what the
 package offered before pcg_policy_pop_sample) against the weights born and refitted on the device.
 
-    python tools/population_search_bench.py [--G 256] [--P 256,4096] [--shapes affine,1x16,2x64] [--reps 5] [--box NAME] [--out FILE]
+    python tools/population_search_bench.py [--G 256] [--P 256,4096] [--shapes affine,1x16,2x64] [--reps 5] [--dtype float32] [--box NAME] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s; one episode = 59 closed-loop steps), P
 members, each scored on G envs (B = P G).  All routes of a comparison alternate inside one process (`reps` rounds after one
@@ -17,6 +17,9 @@ generation starts from the same mean and std (the refit is computed and dropped)
   es-a    numpy: antithetic eps, theta = mean + sigma * eps; update_; evaluate_population; centered ranks to the host;
           mean += lr / (P sigma) * (w @ eps)
   es-b    sample_(antithetic, check=False); evaluate_population; centered_ranks; noise_dot; the update in torch
+
+--dtype float32 times the device routes (eval, cem-b, es-b) of a float32 population and, interleaved in the same process, of the
+fp64 population of the same shape: eval32 / cem32 / es32 against eval64 / cem64 / es64.
 """
 import argparse
 import os
@@ -55,12 +58,14 @@ def case(a, p, name, P, torch, VecEnv, PolicyPopulation, evaluate_population, ce
     dims = [spec.nobs, *SHAPES[name], spec.na]
     L = len(dims) - 1
 
-    def zeros():
+    def zeros(dtype="float64"):
         q = PolicyPopulation([np.zeros((P, dims[l + 1], dims[l])) for l in range(L)], [np.zeros((P, dims[l + 1])) for l in range(L)],
-                             activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0)
+                             activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=dtype)
         q.handle(dev)
         return q
 
+    if a.dtype == "float32":
+        return case_f32(a, env, name, P, zeros("float64"), zeros("float32"), torch, evaluate_population, centered_ranks)
     pop_a, pop_b = zeros(), zeros()
     n = pop_b.n_params
     lay = pop_b.flat_layout()
@@ -119,12 +124,54 @@ def case(a, p, name, P, torch, VecEnv, PolicyPopulation, evaluate_population, ce
     return lines
 
 
+def case_f32(a, env, name, P, pop64, pop32, torch, evaluate_population, centered_ranks):
+    """the device routes of a float32 population and of the fp64 one, interleaved"""
+    G, dev, n = a.G, env.device, pop32.n_params
+    mean_t = torch.zeros(n, dtype=torch.float64, device=dev)
+    std_t = torch.full((n,), 0.5, dtype=torch.float64, device=dev)
+    sig_t = torch.full((n,), SIGMA, dtype=torch.float64, device=dev)
+    keep = {}
+
+    def routes(pop, tag):
+        def f_eval(rep):
+            keep["eval" + tag] = evaluate_population(env, pop, G, gamma=1.0)["score"]
+
+        def cem(rep):
+            pop.sample_(mean_t, std_t, SEED, generation=rep, check=False)
+            score = evaluate_population(env, pop, G, gamma=1.0)["score"]
+            theta = pop.flat(members=torch.topk(score, max(1, P // 10)).indices)
+            keep["cem" + tag] = (theta.mean(dim=0), theta.std(dim=0, unbiased=False) + 0.02)
+
+        def es(rep):
+            pop.sample_(mean_t, sig_t, SEED, generation=rep, antithetic=True, check=False)
+            score = evaluate_population(env, pop, G, gamma=1.0)["score"]
+            g = pop.noise_dot(centered_ranks(score), SEED, generation=rep, antithetic=True)
+            keep["es" + tag] = mean_t + (LR / (P * SIGMA)) * g
+
+        return {"eval" + tag: f_eval, "cem" + tag: cem, "es" + tag: es}
+
+    # (eval runs on what the last generation left in the blocks: one warm-up sample first, so that no route scores zeros)
+    for pop in (pop64, pop32):
+        pop.sample_(mean_t, std_t, SEED, generation=0, check=False)
+    times = timed(torch, {**routes(pop32, "32"), **routes(pop64, "64")}, a.reps)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    lines = [f"{name:7s} P={P:5d} G={G:4d} n={n:5d}   " + "   ".join(f"{k} {med[k]:9.3f}" for k in med) + " ms   "
+             f"eval64 / eval32 = {med['eval64'] / med['eval32']:.2f}   cem64 / cem32 = {med['cem64'] / med['cem32']:.2f}   "
+             f"es64 / es32 = {med['es64'] / med['es32']:.2f}   over the evaluation: cem32 +{med['cem32'] - med['eval32']:.3f} "
+             f"es32 +{med['es32'] - med['eval32']:.3f} cem64 +{med['cem64'] - med['eval64']:.3f} es64 +{med['es64'] - med['eval64']:.3f} ms",
+             "        repeats " + "  ".join(f"{k} {[round(t, 3) for t in v]}" for k, v in times.items())]
+    env.close(), pop64.close(), pop32.close()
+    torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--G", type=int, default=256)
     ap.add_argument("--P", default="256,4096")
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--box", default=socket.gethostname())
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -135,7 +182,7 @@ def main():
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lib = _lib.load()
-    lines = [f"# tools/population_search_bench.py  G={a.G} reps={a.reps}  box {a.box}  library build {lib.pcg_build_id().decode()} "
+    lines = [f"# tools/population_search_bench.py  G={a.G} reps={a.reps} dtype={a.dtype}  box {a.box}  library build {lib.pcg_build_id().decode()} "
              f"({os.path.relpath(_lib.LIB_PATH, ROOT)}, {os.path.getsize(_lib.LIB_PATH)} bytes)  {torch.cuda.get_device_name(0)}",
              "# cstr, RK4 x 1, N = 60: one generation = sample P members, score each on G envs over one episode (59 steps), refit; "
              "wall-clock ms between device synchronisations, median of the interleaved repeats",
