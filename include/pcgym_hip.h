@@ -846,8 +846,19 @@ PCG_API int pcg_step_autoreset(pcg_plan* plan, const pcg_buffers* io, int32_t t,
 /* Step graph: T consecutive pcg_step launches (t = t0 .. t0+T-1, optionally preceded by a full pcg_reset)
  * recorded once as a HIP graph and replayed with ONE host call.  This is the on-device form of the
  * reference's per-episode Python loop "for i in range(N-1): env.step(a_i)" (policy_evaluation.py:86-128)
- * for callers that still want every step's obs/rew in the plan's buffers between launches: same kernels,
+ * for callers that still want every step's obs/rew in the plan's buffers between launches: same results,
  * same buffers, no launch-to-launch gap (measured 15.0 -> 13.6 us per step on the 2^20-env cstr workload).
+ * INVARIANT: after every recorded LAUNCH every buffer holds the bytes the pcg_step loop leaves at that point.
+ * A launch is one step, except that a run of two or more consecutive steps that would each take the lean pipelined RK4
+ * kernel (lock-stepped plans of the small models with none of the extras, no d_steps, B < 2^28, no forced
+ * PCG_OPT_VARIANT / PCG_OPT_STREAM_BLOCKS_PER_CU) is recorded as ONE chained launch: every tile of envs keeps its state in
+ * registers from the run's first step to its last, and no step waits for the whole batch to finish the one before it.
+ * Every step of the run still stores its observation, reward and done bytes, in step order, so after the launch obs / rew
+ * / done are the last step's and x is the final state; the states between the run's steps are never in memory (nothing
+ * can read the buffers inside a replay).  The sticky status byte is written once per chained launch (a non-finite state
+ * stays non-finite).  Two envs per lane only if every a_steps[j] of the run is 16-byte aligned.  The graph owns a small
+ * device table of the run's action pointers, allocated before the recording and freed by pcg_graph_destroy.
+ * PCG_NO_CHAIN set in the environment when the plan was created: every step is a launch of its own.
  * a_steps [T] device pointers, each [na][B] (entries may repeat); d_steps NULL or [T] pointers, each [nd][B].
  * t0, T, seed and all buffer addresses are baked into the graph; pcg_graph_set_seed() re-keys the RNG of an
  * instantiated graph (new episode, fresh noise) without re-recording.  io->t must be NULL (lock-stepped). */
@@ -861,10 +872,14 @@ PCG_API int pcg_graph_destroy(pcg_graph* graph);
  * of the extras, RK4 / CV8) that directly follows another one skips the observation's set-point / disturbance slot rows
  * when the schedules give both steps bitwise the same values, and the done bytes when both steps set the same flag.  The
  * first recorded step stores everything, so a replay never depends on what the buffers held before it, and after every
- * node every buffer holds exactly the bytes T pcg_step calls would have left.  *slot_nodes / *done_nodes (either may be
+ * launch every buffer holds exactly the bytes the pcg_step calls up to there would have left.  *slot_nodes / *done_nodes (either may be
  * NULL): how many recorded steps skip the slot rows / the done bytes; both 0 for graphs of any other kernel and with
  * PCG_NO_HELD_ROWS set in the environment when the plan was created. */
 PCG_API int pcg_graph_held(const pcg_graph* graph, int32_t* slot_nodes, int32_t* done_nodes);
+/* *launches / *steps (either may be NULL): how many chained launches the graph holds and how many of its recorded steps
+ * they cover; both 0 where no run of two chainable steps exists and with PCG_NO_CHAIN.  pcg_graph_held counts a chained
+ * step like any other recorded step, and pcg_graph_set_seed re-keys chained launches too. */
+PCG_API int pcg_graph_chained(const pcg_graph* graph, int32_t* launches, int32_t* steps);
 
 /* Compiler output of the most recent failed run-time compilation in this process (static storage, "" if none). */
 PCG_API const char* pcg_last_jit_log(void);

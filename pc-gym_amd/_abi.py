@@ -238,6 +238,7 @@ EXPORTS = [
     "pcg_graph_set_seed",
     "pcg_graph_destroy",
     "pcg_graph_held",
+    "pcg_graph_chained",
     "pcg_last_jit_log",
     "pcg_philox4x32_10",
     "pcg_test_sort_tile",
@@ -363,6 +364,8 @@ def declare(lib):
     lib.pcg_graph_destroy.argtypes = [vp]
     lib.pcg_graph_held.restype = C.c_int
     lib.pcg_graph_held.argtypes = [vp, _pi, _pi]
+    lib.pcg_graph_chained.restype = C.c_int
+    lib.pcg_graph_chained.argtypes = [vp, _pi, _pi]
     lib.pcg_last_jit_log.restype = C.c_char_p
     lib.pcg_last_jit_log.argtypes = []
     lib.pcg_test_sort_tile.restype = C.c_int

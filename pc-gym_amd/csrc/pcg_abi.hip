@@ -127,7 +127,8 @@ struct pcg_plan {
   // reference paths the tests select through the environment, read at creation: PCG_NO_FIXUP (guarded plans in one
   // launch), PCG_NO_FLAT (the single-kernel rollout), PCG_Q_FORCE_LEAN (the lean queue layout wherever it fits)
   // ... and PCG_NO_HELD_ROWS: recorded step graphs store every row in every node (pcg_graph_create; A/B)
-  bool no_fixup, no_flat, q_force_lean, no_held;
+  // ... and PCG_NO_CHAIN: they record every step as a launch of its own (A/B, and the way back should a chain misbehave)
+  bool no_fixup, no_flat, q_force_lean, no_held, no_chain;
   int64_t env_offset;
   DevConst hc;       // host copy
   DevConst* dC;      // device copy
@@ -1037,6 +1038,7 @@ int pcg_plan_create(pcg_plan** out, const pcg_env_cfg* cfg) {
   p->no_flat = std::getenv("PCG_NO_FLAT") != nullptr;
   p->q_force_lean = std::getenv("PCG_Q_FORCE_LEAN") != nullptr;
   p->no_held = std::getenv("PCG_NO_HELD_ROWS") != nullptr;
+  p->no_chain = std::getenv("PCG_NO_CHAIN") != nullptr;
   p->nx = cfg->nx;  // (every other field starts zeroed)
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&p->num_cus, hipDeviceAttributeMultiprocessorCount, p->device);
@@ -1376,7 +1378,15 @@ static bool step_queue(StepCall& s, int* rc) {
 // Adaptive stepping is left to the one-wave-per-workgroup classic kernel unless a streaming variant is forced:
 // lanes take different numbers of steps, and a persistent grid fixes each wave's share of the batch up front,
 // whereas the dispatcher hands single-wave workgroups to whichever SIMD slot frees first.
-static bool step_lean(StepCall& s, int* rc) {
+// (the choice on its own, as feat_pick is: also asked by pcg_graph_create, which records a run of the pipelined RK4 kernel's
+// steps as one chained launch.  False: the route leaves the launch.  Otherwise *rc is PCG_OK and *o the launch, or an error.)
+struct LeanPick {
+  StepFn fn;
+  int e;          // envs per lane - 1
+  bool piped;     // the software-pipelined kernel
+  int64_t grid;
+};
+static bool lean_pick(const StepCall& s, LeanPick* o, int* rc) {
   const pcg_plan* p = s.p; const Kernels& k = s.k; const pcg_buffers* io = s.io;
   const int integ = p->integrator_id, v = p->variant;
   const int ls = lean_scheme(integ);  // fixed-step schemes with a lean pipelined kernel (RK4, CV8)
@@ -1405,14 +1415,22 @@ static bool step_lean(StepCall& s, int* rc) {
   if (piped && bpc > 5) bpc = 5;
   if (p->stream_bpc > 0 && p->stream_bpc <= occ) bpc = p->stream_bpc;
   const int64_t grid = std::min((int64_t)p->num_cus * bpc, (io->B + BLOCK * (e + 1) - 1) / (BLOCK * (e + 1)));
-  s.a.nt_stores = p->nt_stores;
+  *o = LeanPick{fn, e, piped, grid};
+  return taken(rc, PCG_OK);
+}
+
+static bool step_lean(StepCall& s, int* rc) {
+  LeanPick k;
+  if (!lean_pick(s, &k, rc)) return false;
+  if (*rc != PCG_OK) return true;
+  s.a.nt_stores = s.p->nt_stores;
   // rows the previous node of a step graph left with this step's bytes: only the pipelined kernel skips them, and its
   // auto-reset instantiation never does
-  if (piped && !s.auto_reset) {
+  if (k.piped && !s.auto_reset) {
     s.a.held = s.held;
     s.route = ROUTE_LEAN_PIPE;
   }
-  hipLaunchKernelGGL(cov(fn), dim3((unsigned)grid), dim3(BLOCK), 0, s.st, s.a);
+  hipLaunchKernelGGL(cov(k.fn), dim3((unsigned)k.grid), dim3(BLOCK), 0, s.st, s.a);
   return taken(rc, (int)hipGetLastError());
 }
 
@@ -1524,6 +1542,41 @@ static int step_impl(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t see
   }
   if (route) *route = ROUTE_CLASSIC;
   return step_classic(s);
+}
+
+// Would step_impl hand the plain step t on these buffers to step_lean's pipelined RK4 kernel (ROUTE_LEAN_PIPE), unforced?
+// *e: its envs per lane - 1.  Launches nothing, changes nothing (pcg_graph_create: which steps may join a chained launch).
+static bool lean_pipe_rk4(const pcg_plan* p, const pcg_buffers* io, int32_t t, int* e) {
+  StepArgs a;
+  if (fill_args(p, io, &a) != PCG_OK || io->B <= 0 || !io->x || !io->a || !io->obs || !io->rew || !io->done || io->t || t < 0)
+    return false;
+  // the routes ahead of step_lean: run-time compiled plans and per-env parameters never get there (step_jit, step_unc;
+  // step_queue takes adaptive plans only); a forced variant or grid is somebody's measurement of the per-step kernels
+  if (p->integrator_id != PCG_INT_RK4 || p->jit_fn[0] || p->hc.nunc > 0 || p->variant != 0 || p->stream_bpc > 0) return false;
+  const Kernels& k = kernels(p->kid);
+  const bool lds_st = lds_stages_on(p, k);
+  const StepCall s{p, k, io, a, 0, lds_st, has_extras(p->hc, io), false, 0, 0, nullptr, 0, ROUTE_NONE};
+  LeanPick pick;
+  int rc = PCG_OK;
+  if (!lean_pick(s, &pick, &rc) || rc != PCG_OK || !pick.piped || !k.chain[pick.e]) return false;
+  *e = pick.e;
+  return true;
+}
+
+// The n steps t .. t + n - 1 of `steps` (device table: action rows and held words) as ONE launch of step_chain_kernel: one
+// workgroup per tile, every tile on its own from its first load to its last store.
+static int chain_launch(const pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, int32_t n, const ChainStep* steps, int e,
+                        hipStream_t st) {
+  StepArgs a;
+  PCG_TRY(fill_args(p, io, &a));
+  a.t_scalar = t;
+  a.seed = seed;
+  a.T = n;
+  a.chain = (const PCG_CONSTANT ChainStep*)steps;
+  a.nt_stores = p->nt_stores;
+  const int64_t tile = (int64_t)BLOCK * (e + 1);
+  hipLaunchKernelGGL(cov(kernels(p->kid).chain[e]), dim3((unsigned)((io->B + tile - 1) / tile)), dim3(BLOCK), 0, st, a);
+  return (int)hipGetLastError();
 }
 
 int pcg_step(pcg_plan* p, const pcg_buffers* io, int32_t t, uint64_t seed, void* stream) {
@@ -2557,6 +2610,8 @@ struct pcg_graph {
   hipGraphExec_t exec;
   int n_nodes;
   int slot_nodes, done_nodes;  // recorded steps that skip the observation's slot rows / the done bytes (pcg_graph_held)
+  int chain_launches, chain_steps;  // chained launches and the recorded steps they cover (pcg_graph_chained)
+  ChainStep* dchain;           // [T] device table of the chained steps (null without a chain): owned, freed with the graph
 };
 static constexpr uint32_t GRAPH_MAGIC = 0x50434747u;  // 'PCGG'
 
@@ -2579,9 +2634,17 @@ static int32_t held_rows(const pcg_plan* p, int32_t t) {
 // Rows that carry nothing new are not stored twice: a node that runs step_lean's pipelined kernel directly after another
 // one that did skips the stores of held_rows().  Node 0 of the steps never skips anything, with or without with_reset (the
 // reset kernel writes other slot values and no done bytes), so a replay does not depend on what the buffers held before
-// it.  INVARIANT: after every node every buffer holds exactly the bytes it would hold with every store made -- replays
-// are bit-identical to T pcg_step calls, and a concurrent reader of the buffers sees no difference either.
+// it.  INVARIANT: after every recorded LAUNCH every buffer holds exactly the bytes the pcg_step loop leaves at that point --
+// replays are bit-identical to T pcg_step calls.
 // PCG_NO_HELD_ROWS (read at plan creation) records every store (A/B measurement, tests).
+// A launch is one step, except for chains: a maximal run of at least two consecutive steps that would each take step_lean's
+// pipelined RK4 kernel unforced (lean_pipe_rk4), without d_steps, is recorded as ONE launch of step_chain_kernel -- a tile's
+// state stays in registers from the run's first step to its last, every step still stores its observation, reward and
+// (unless held) slot rows and done bytes, the state goes back once.  Two envs per lane only if every step of the run would
+// have had them (every a_steps[j] 16-byte aligned).  The held word of each step is held_rows() as before, chained or not,
+// so pcg_graph_held counts the same steps.  The steps' action pointers and held words are a device table the graph owns,
+// on the device before the capture begins; nothing is allocated or freed on the launch path.  PCG_NO_CHAIN (read at plan
+// creation) records one launch per step (A/B measurement, the way back).  n_nodes keeps counting recorded steps (+ reset).
 int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const double* const* a_steps,
                      const double* const* d_steps, int32_t t0, int32_t T, uint64_t seed, int with_reset) {
   if (!out) return PCG_E_NULL;
@@ -2593,19 +2656,73 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
   for (int j = 0; j < T; ++j)
     if (!a_steps[j] || (d_steps && !d_steps[j])) return PCG_E_NULL;
   pcg_buffers b = *io;
+  // run[j]: steps in the chained launch that starts at step j (0: step j is a launch of its own, or inside a chain);
+  // epl[j]: envs per lane - 1 of the pipelined kernel that would take step j alone, -1 where another kernel would
+  std::vector<int> run((size_t)T, 0), epl((size_t)T, -1);
+  int chain_launches = 0, chain_steps = 0;
+  if (!p->no_chain && !d_steps)
+    for (int j = 0; j < T; ++j) {
+      b.a = a_steps[j];
+      int e1 = 0;
+      if (lean_pipe_rk4(p, &b, t0 + j, &e1)) epl[(size_t)j] = e1;
+    }
+  for (int j = 0; j < T;) {
+    int n = 0;
+    while (j + n < T && epl[(size_t)(j + n)] >= 0) ++n;
+    if (n >= 2) {
+      run[(size_t)j] = n;
+      ++chain_launches;
+      chain_steps += n;
+    }
+    j += n > 0 ? n : 1;
+  }
+  // the chained steps' table: filled and on the device BEFORE the capture begins; nothing is allocated on the launch path
+  std::vector<ChainStep> hchain((size_t)T, ChainStep{nullptr, 0});
+  ChainStep* dchain = nullptr;
+  if (chain_launches > 0) {
+    // (the route of the step ahead of step j: a chained step is the pipelined kernel's, as is one it would have taken alone)
+    for (int j = 0; j < T; ++j) {
+      hchain[(size_t)j].a = a_steps[j];
+      hchain[(size_t)j].held = (j > 0 && epl[(size_t)(j - 1)] >= 0) ? held_rows(p, t0 + j) : 0;
+    }
+    HIP_TRY(hipMalloc((void**)&dchain, sizeof(ChainStep) * (size_t)T));
+    const hipError_t ec = hipMemcpy(dchain, hchain.data(), sizeof(ChainStep) * (size_t)T, hipMemcpyHostToDevice);
+    if (ec != hipSuccess) {
+      (void)hipFree(dchain);
+      return (int)ec;
+    }
+  }
   hipStream_t cs;
-  HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  int rc = PCG_OK;
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+  hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+  if (e == hipSuccess) {
+    e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) (void)hipStreamDestroy(cs);
+  }
   if (e != hipSuccess) {
-    (void)hipStreamDestroy(cs);
+    if (dchain) (void)hipFree(dchain);
     return (int)e;
   }
+  int rc = PCG_OK;
+  hipGraph_t g = nullptr;
   if (with_reset) rc = pcg_reset(p, &b, nullptr, seed, cs);
   int slot_nodes = 0, done_nodes = 0;
   StepRoute prev = ROUTE_NONE;
-  for (int j = 0; j < T && rc == PCG_OK; ++j) {
+  for (int j = 0; j < T && rc == PCG_OK;) {
+    const int n = run[(size_t)j];
+    if (n >= 2) {  // steps j .. j + n - 1 as one launch; two envs per lane where every one of them would have had them
+      int e1 = 1;
+      for (int i = 0; i < n; ++i) e1 = std::min(e1, epl[(size_t)(j + i)]);
+      b.a = a_steps[j];
+      b.d = nullptr;
+      rc = chain_launch(p, &b, t0 + j, seed, n, dchain + j, e1, cs);
+      for (int i = 0; i < n; ++i) {
+        slot_nodes += hchain[(size_t)(j + i)].held & 1;
+        done_nodes += (hchain[(size_t)(j + i)].held >> 1) & 1;
+      }
+      prev = ROUTE_LEAN_PIPE;
+      j += n;
+      continue;
+    }
     b.a = a_steps[j];
     b.d = d_steps ? d_steps[j] : nullptr;
     const int32_t held = (j > 0 && prev == ROUTE_LEAN_PIPE) ? held_rows(p, t0 + j) : 0;
@@ -2614,25 +2731,21 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
       slot_nodes += held & 1;
       done_nodes += (held >> 1) & 1;
     }
+    ++j;
   }
   e = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);
-  if (rc != PCG_OK) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
-  if (e != hipSuccess) return (int)e;
   hipGraphExec_t ex = nullptr;
-  e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-  if (e != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    return (int)e;
+  if (rc == PCG_OK && e == hipSuccess) {
+    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) ex = nullptr;
   }
-  pcg_graph* q = new (std::nothrow) pcg_graph();
+  pcg_graph* q = (rc == PCG_OK && e == hipSuccess) ? new (std::nothrow) pcg_graph() : nullptr;
   if (!q) {
-    (void)hipGraphExecDestroy(ex);
-    (void)hipGraphDestroy(g);
-    return PCG_E_VALUE;
+    if (ex) (void)hipGraphExecDestroy(ex);
+    if (g) (void)hipGraphDestroy(g);
+    if (dchain) (void)hipFree(dchain);
+    return rc != PCG_OK ? rc : e != hipSuccess ? (int)e : PCG_E_VALUE;
   }
   q->magic = GRAPH_MAGIC;
   q->device = p->device;
@@ -2641,7 +2754,17 @@ int pcg_graph_create(pcg_graph** out, pcg_plan* p, const pcg_buffers* io, const 
   q->n_nodes = T + (with_reset ? 1 : 0);
   q->slot_nodes = slot_nodes;
   q->done_nodes = done_nodes;
+  q->chain_launches = chain_launches;
+  q->chain_steps = chain_steps;
+  q->dchain = dchain;
   *out = q;
+  return PCG_OK;
+}
+
+int pcg_graph_chained(const pcg_graph* q, int32_t* launches, int32_t* steps) {
+  if (!q || q->magic != GRAPH_MAGIC) return PCG_E_PLAN;
+  if (launches) *launches = q->chain_launches;
+  if (steps) *steps = q->chain_steps;
   return PCG_OK;
 }
 
@@ -2688,6 +2811,7 @@ int pcg_graph_destroy(pcg_graph* q) {
   if (q->magic != GRAPH_MAGIC) return PCG_E_PLAN;
   (void)hipGraphExecDestroy(q->exec);
   (void)hipGraphDestroy(q->graph);
+  if (q->dchain) (void)hipFree(q->dchain);
   q->magic = 0;
   delete q;
   return PCG_OK;

@@ -141,8 +141,15 @@ struct LeanStep {
   double ud[PCG_MAX_NDM];   // model disturbance inputs held over the step (defaults, overridden by the configured ones)
 };
 
+// One step of a chained launch (step_chain_kernel, pcg_lean.hpp): its action rows and its StepArgs::held word.  A device
+// table owned by the step graph that records the launch (pcg_graph_create); wave-uniform, read with scalar loads.
+struct ChainStep {
+  const double* a;
+  int32_t held;
+};
+
 struct StepArgs {
-  CDevConst* C;                       // constant address space: uniform reads -> s_load
+  CDevConst* C;                      // constant address space: uniform reads -> s_load
   const PCG_CONSTANT double* sched;   // [nsp + nd][N]
   const PCG_CONSTANT LeanStep* lean;  // [N] (lock-stepped lean kernels)
   double* x;
@@ -170,8 +177,14 @@ struct StepArgs {
   int32_t q_tile;        // work-queue kernel: slots of the LDS tile | QT_* flags (below); flat rollout: its step cadence
   int32_t auto_reset;    // per-env-t kernels: reset the envs that finished in this step (pcg_step_autoreset)
   uint64_t reset_seed;   // RNG key of those resets
-  // rollout
-  const double* a_seq;
+  // rollout: the T steps from t_scalar, their actions one sequence ...
+  // ... or, for the chained launch of a recorded step graph (step_chain_kernel), one table entry per step.  The two share
+  // the slot: StepArgs keeps its size and every field its offset, so every other kernel -- those that take a second
+  // by-value argument behind StepArgs included -- keeps its kernarg layout and its code.
+  union {
+    const double* a_seq;
+    const PCG_CONSTANT ChainStep* chain;  // [T]
+  };
   double* obs_seq;
   double* rew_seq;
   // element strides of the sequences: (step, component); the env index is always unit-stride
@@ -1244,6 +1257,7 @@ struct Kernels {
   size_t (*queue_lds_x_lean)(int, int);  // ... in the lean layout (tile size, stored input rows: pcg_step_queue.hpp QTile)
   StepFn pipe[2][2];                 // software-pipelined lean kernel [lean_scheme(integrator)][EPL-1] (may be null)
   StepFn pipe_ar[2][2];              // the same with the same-launch auto-reset path compiled in
+  StepFn chain[2];                   // a run of RK4 steps of a recorded step graph as one launch [EPL-1] (where pipe[0] exists)
   StepFn roll_lean[2];               // RK4 lean fused rollout [EPL-1] (may be null)
   StepFn rollout[PCG_INT_COUNT][2];  // [integrator][lds_stages]
   StepFn rollout_unc[PCG_INT_COUNT]; // fused rollout with per-env parameters (RK4, DOPRI5; null for affine)
@@ -1405,6 +1419,8 @@ Kernels make_kernels() {
       k.pipe[0][1] = step_kernel_pipe<M, 2>;
       k.pipe_ar[0][0] = step_kernel_pipe<M, 1, true>;
       k.pipe_ar[0][1] = step_kernel_pipe<M, 2, true>;
+      k.chain[0] = step_chain_kernel<M, 1>;
+      k.chain[1] = step_chain_kernel<M, 2>;
       // the order-8 scheme keeps more stage vectors alive: two envs per lane only where that fits 128 registers (four
       // waves per SIMD, and room beside the work-queue kernels of a mixed batch) without spilling
       k.pipe[1][0] = step_kernel_pipe<M, 1, false, PCG_INT_CV8>;

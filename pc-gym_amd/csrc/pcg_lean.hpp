@@ -191,6 +191,18 @@ PCG_DEV void put_obs_rows(const Rows obs, const Lane at, int nx, int nso, int nd
     if (i < nx) put<EPL>(at(obs.base + (size_t)i * obs.stride), ox[i].v, obs.nt);
   put_slot_rows<M, EPL>(obs, at, nx, nso, nd, osp, od);
 }
+// ... with `hold` as in put_state_rows (step_chain_kernel: every step of a chain but its last)
+template <class M, int EPL, class Lane, class SP, class D>
+PCG_DEV void put_obs_rows(const Rows obs, const Lane at, int nx, int nso, int nd, const Pack<EPL> (&ox)[M::NX], const SP& osp,
+                          const D& od, bool hold) {
+#pragma unroll
+  for (int i = 0; i < M::NX; ++i)
+    if (i < nx) put<EPL>(at(obs.base + (size_t)i * obs.stride), ox[i].v, obs.nt);
+  if (!hold) {
+    put_slot_rows<M, EPL>(obs, at, nx, nso, nd, osp, od);
+    asm volatile("");  // keep it a (scalar) branch
+  }
+}
 template <class M, int EPL, class Lane, class SP, class D>
 PCG_DEV void put_state_rows(const Rows x, const Rows obs, const Lane at, int nx, int nso, int nd, const Pack<EPL> (&xs)[M::NX],
                             const Pack<EPL> (&ox)[M::NX], const SP& osp, const D& od, bool hold = false) {
@@ -493,6 +505,109 @@ __global__ __launch_bounds__(BLOCK, INTEG == PCG_INT_RK4 ? PCG_LEAN_WPE : 4) voi
     for (int i = 0; i < NX; ++i) xv[i] = xn[i];
 #pragma unroll
     for (int i = 0; i < NA; ++i) av[i] = an[i];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// A run of consecutive step_kernel_pipe nodes of a recorded step graph as ONE launch (pcg_graph_create): A.T steps from
+// t = A.t_scalar on one tile of BLOCK * EPL envs per workgroup, the state in registers from the first load to the last
+// store.  Tile i of step j + 1 depends on tile i of step j alone, and nothing outside the graph can touch the buffers
+// between two of its nodes: the launch boundary was a grid-wide barrier, and the state's round trip through memory a pass,
+// that the result does not need.  Every step still stores what its holding node stored, in that order -- observation rows,
+// the slot rows and done bytes unless held (ChainStep::held), the reward -- through the same env_step_lean call, so the
+// bytes are step_kernel_pipe's.  The state goes back once, after the last step; the sticky status byte is written once,
+// at the end (a non-finite state is absorbing, as in rollout_kernel_lean).  No workgroup waits for another one.
+//
+// Actions arrive in groups of PCG_CHAIN_D steps: the next group's rows are requested before the current group is
+// integrated, and ONE land() per group waits for them.  Loads and stores share the vmcnt counter, so that wait also meets
+// the stores of the group's last step -- once per PCG_CHAIN_D steps, where rollout_kernel_lean's per-step land() meets every
+// step's.  (D, waves per SIMD asked of the register allocator) by measurement: profiles/r21/graph_chain.txt.
+// ---------------------------------------------------------------------------
+#ifndef PCG_CHAIN_D
+#define PCG_CHAIN_D 2
+#endif
+// waves per SIMD asked of the register allocator: the most at which the kernel stays out of scratch at that D
+// (nx = 2: cstr, nx = 4: four_tank; PCG_CHAIN_WPE overrides, for the measurement builds)
+constexpr int chain_wpe(int nx, int epl) {
+#ifdef PCG_CHAIN_WPE
+  return PCG_CHAIN_WPE;
+#else
+  return nx <= 2 ? (epl == 1 ? 7 : 6) : (epl == 1 ? 5 : 4);
+#endif
+}
+template <class M, int EPL>
+__global__ __launch_bounds__(BLOCK, chain_wpe(M::NX, EPL)) void step_chain_kernel(const StepArgs A) {
+  CDevConst& c = *A.C;
+  constexpr int NX = M::NX, NA = M::NA, D = PCG_CHAIN_D;
+  using V = typename Vec<EPL>::T;
+  const uint32_t B = (uint32_t)A.B;  // < 2^28 (pcg_graph_create), as in step_kernel_pipe
+  const size_t Bs = (size_t)A.B;
+  const int nx = M::DYNAMIC ? c.nx : NX;
+  const int na = M::DYNAMIC ? c.na : NA;
+  const int n = A.T;
+  const PCG_CONSTANT ChainStep* const cs = A.chain;
+  const bool nt = (A.nt_stores & 1) != 0;
+  const bool ntl = (A.nt_stores & 4) != 0;
+  const uint32_t e0 = (blockIdx.x * (uint32_t)BLOCK + threadIdx.x) * EPL;
+  if (e0 >= B) return;
+  const uint32_t o8 = e0 * 8u;
+  const LaneOff8 at{o8};
+  V xv[NX], an[D][NA] = {};
+  // the action rows of steps s0 .. s0 + D - 1 (those the chain has)
+  auto fetch = [&](int s0) {
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+      if (s0 + d < n) {
+        const double* const a = cs[s0 + d].a;
+#pragma unroll
+        for (int i = 0; i < NA; ++i)
+          if (i < na) an[d][i] = ntl ? Vec<EPL>::load_nt(row_at<double>(a + (size_t)i * Bs, o8)) : *row_at<V>(a + (size_t)i * Bs, o8);
+      }
+  };
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+    if (i < nx) xv[i] = ntl ? Vec<EPL>::load_nt(row_at<double>(A.x + (size_t)i * Bs, o8)) : *row_at<V>(A.x + (size_t)i * Bs, o8);
+  fetch(0);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) land(xv[i]);
+  Pack<EPL> xs[NX];
+  unpack<NX, EPL>(xv, nx, xs);
+  const Rows obs{A.obs, Bs, nt};
+  for (int s0 = 0; s0 < n; s0 += D) {
+    Pack<EPL> as[D][NA];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) land(an[d][i]);
+      unpack<NA, EPL>(an[d], na, as[d]);
+    }
+    asm volatile("" ::: "memory");
+    if (s0 + D < n) fetch(s0 + D);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int s = s0 + d;
+      if (s < n) {
+        const int t = A.t_scalar + s;
+        const PCG_CONSTANT LeanStep& L = A.lean[min(t, c.N - 1)];
+        int32_t held = cs[s].held;
+        asm volatile("" : "+s"(held));  // (its two tests stay scalar branches, as in store_lean)
+        LeanOut<M, EPL> out;
+        env_step_lean<M, EPL>(A, c, L, t, as[d], xs, out);
+        if (s + 1 < n) {
+          put_obs_rows<M, EPL>(obs, at, nx, c.nsp_obs, c.nd, out.ox, L.osp, L.od, (held & 1) != 0);
+        } else {  // the last step: the state goes back in place, row by row ahead of its observation row
+          if (A.status) flag_nonfinite<NX, EPL>(A.status, e0, xs);
+          put_state_rows<M, EPL>(Rows{A.x, Bs, (A.nt_stores & 2) != 0}, obs, at, nx, c.nsp_obs, c.nd, xs, out.ox, L.osp, L.od,
+                                 (held & 1) != 0);
+        }
+        put<EPL>(at(A.rew), out.rew.v, nt);
+        if (!(held & 2)) {
+          put_done<EPL>(A.done + e0, out.done);
+          asm volatile("");  // keep it a (scalar) branch
+        }
+      }
+    }
   }
 }
 

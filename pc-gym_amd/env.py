@@ -185,9 +185,21 @@ class VecEnv:
         """(B, Nobs) view of the SoA observation storage."""
         return self.obs_soa.t()
 
+    # steps run by step() / by replays of recorded graphs, and the bytes per env the latter moved (bytes_per_env_step)
+    _eager_steps = 0
+    _graph_steps = 0
+    _graph_bytes = 0
+
     @property
     def bytes_per_env_step(self):
-        return int(self._lib.pcg_plan_bytes_per_env_step(self._plan, self._bufp))
+        """Algorithmic bytes per env step: what a pcg_step launch of this plan and buffer set moves
+        (pcg_plan_bytes_per_env_step).  Once recorded step graphs have been replayed, the mean over every step this env
+        has run of what its launch moves: a recorded step does not store rows the step before it left unchanged, and
+        the steps of a chained launch share one read and one write of the state (StepGraph.bytes_per_env)."""
+        a = int(self._lib.pcg_plan_bytes_per_env_step(self._plan, self._bufp))
+        if not self._graph_steps:
+            return a
+        return int(round((a * self._eager_steps + self._graph_bytes) / (self._eager_steps + self._graph_steps)))
 
     def _episode_seed(self):
         return (self.seed0 + self.episode) & 0xFFFFFFFFFFFFFFFF
@@ -275,6 +287,7 @@ class VecEnv:
             _lib.check(self._lib.pcg_step(self._plan, self._bufp, self.t, self._episode_seed(), self._stream()),
                        "pcg_step")
         self.t += 1
+        self._eager_steps += 1
         if fused_reset and not self.per_env_t:
             self.t = 0  # the new episode started inside the launch
         info = {}
@@ -551,6 +564,13 @@ class StepGraph:
             _lib.check(env._lib.pcg_graph_create(C.byref(g), env._plan, env._bufp, ap, dp, self.t0, T, self._seed,
                                                  int(self.with_reset)), "pcg_graph_create")
         self._g = g
+        # bytes per env that one replay's steps move: the pcg_step formula for each, less the slot rows (8 B each) and done
+        # bytes that holding steps do not store, less the state's read and write (16 B per state) of every chained step but
+        # one per chained launch
+        slot, done = self.held
+        launches, chained = self.chained
+        self.bytes_per_env = (T * int(env._lib.pcg_plan_bytes_per_env_step(env._plan, env._bufp)) - 8 * (s.nsp_obs + s.nd) * slot
+                              - done - 16 * s.nx * (chained - launches))
 
     @property
     def held(self):
@@ -562,6 +582,17 @@ class StepGraph:
         ns, nd = C.c_int32(0), C.c_int32(0)
         _lib.check(self.env._lib.pcg_graph_held(self._g, C.byref(ns), C.byref(nd)), "pcg_graph_held")
         return ns.value, nd.value
+
+    @property
+    def chained(self):
+        """(launches, steps): how many chained launches the graph holds -- runs of consecutive lean pipelined RK4 steps
+        recorded as ONE kernel launch each, the state in registers from the run's first step to its last -- and how many
+        of the recorded steps they cover (pcg_graph_chained).  (0, 0) with PCG_NO_CHAIN set when the env was created."""
+        if self._g is None:
+            raise RuntimeError("StepGraph was destroyed")
+        nl, ns = C.c_int32(0), C.c_int32(0)
+        _lib.check(self.env._lib.pcg_graph_chained(self._g, C.byref(nl), C.byref(ns)), "pcg_graph_chained")
+        return nl.value, ns.value
 
     def replay(self):
         """Run the recorded steps on the current stream; returns (obs, rew, done) of the last one."""
@@ -581,6 +612,8 @@ class StepGraph:
             self._seed = seed
         _lib.check(env._lib.pcg_graph_launch(self._g, env._stream()), "pcg_graph_launch")
         env.t = self.t0 + self.T
+        env._graph_steps += self.T
+        env._graph_bytes += self.bytes_per_env
         return env.obs, env.rew, env.done.view(_torch().bool)
 
     def destroy(self):
