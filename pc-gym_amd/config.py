@@ -978,7 +978,7 @@ class EnvSpec:
         if self.nunc > abi.PCG_MAX_NUNC:
             raise ValueError(f"at most {abi.PCG_MAX_NUNC} uncertain parameters are supported")
         # (an inert key takes the first index past the model's parameters: the kernels substitute it into
-        # nothing, pcg_abi.hip accepts it for empirical tables only)
+        # nothing, pcg_abi_cfg.hip accepts it for empirical tables only)
         self.unc_index = np.array([names.index(k) if k in names else len(names) for k in self.unc_keys], dtype=np.int32)
         self.unc_pct = np.array([float(up[k]) for k in self.unc_keys], dtype=_f64)
         self.unc_emp, self.unc_emp_off = _empirical_tables(emp, self.unc_keys)

@@ -3,7 +3,7 @@
 // collector that is itself one launch.  Interface after stable-baselines3's RolloutBuffer.compute_returns_and_advantage
 // (its next_non_terminal is `!cut` here).
 //
-// One env per lane (two where the host found 16-byte accesses possible: gae_vec2_ok in pcg_abi.hip), backwards in time:
+// One env per lane (two where the host found 16-byte accesses possible: gae_vec2_ok in pcg_abi_policy.hip), backwards in time:
 //
 //     cut   = term ? term[t] != 0 : false;   the last step is cut as well unless bootstrap_last
 //     nxt   = cut ? 0.0 : val[t+1]           c = cut ? 0.0 : carry

@@ -1,7 +1,7 @@
 // pcg_kernels.hpp -- device code shared by every translation unit of libpcgym_hip.so: the fused
 // environment-step / rollout / test-hook kernel templates and make_kernels<ID>() (the table of
 // instantiations for one model).  pcg_inst_*.hip instantiate groups of models so that the library
-// builds in parallel; pcg_abi.hip holds the C ABI, the host dispatch and the reset kernel.
+// builds in parallel; pcg_abi.hip and its pcg_abi_*.hip siblings hold the C ABI, the host dispatch and the reset kernel.
 //
 //
 // Execution model
@@ -133,7 +133,7 @@ struct DevConst {
 using CDevConst = const PCG_CONSTANT DevConst;
 
 // Wave-uniform values of one lock-stepped step t -> t + 1 (lean plans), folded on the host at plan creation
-// (pcg_abi.hip: lean_table): what env_step_lean() used to compute on the vector unit once per tile.
+// (pcg_abi_cfg.hip: lean_table): what env_step_lean() used to compute on the vector unit once per tile.
 struct LeanStep {
   double osp[PCG_MAX_NSP];  // observation SP slots, normalised: SP[k][min(t, N-1)]                (quirk Q5)
   double spn[PCG_MAX_NSP];  // reward set-points SP[k][min(t+1, N-1)]
@@ -193,7 +193,7 @@ struct StepArgs {
   float q_w;             // work-queue kernel: weight of ln(scaled |f(x0)|) in the sort key (the transient's share)
   int32_t q_prio;        // work-queue kernel: waves holding one of the q_prio heaviest envs of their tile raise their issue
                          // priority (0 = off); workgroups of the upper half of the grid start their heaviest envs two waves on
-  int32_t fixup;         // guarded plans in two launches (pcg_abi.hip): 1 = the general kernel leaves an env the guard does not
+  int32_t fixup;         // guarded plans in two launches (pcg_abi_step.hip): 1 = the general kernel leaves an env the guard does not
                          // trust untouched and marks it (done[e] = PCG_DONE_PENDING), the work-queue kernel then integrates
                          // exactly the marked envs with the adaptive pair and finishes their step
   int32_t held;          // step_kernel_pipe inside a recorded step graph (pcg_graph_create), 0 everywhere else: bit 0 = the
@@ -206,7 +206,7 @@ struct StepArgs {
 };
 
 // The q_tile word of a work-queue launch: tile slots in the low bits, then how the tile is laid out in LDS and how many
-// waves of a workgroup take part in the cooperative phase (written by pcg_abi.hip, read by pcg_step_queue.hpp)
+// waves of a workgroup take part in the cooperative phase (written by pcg_abi_step.hip, read by pcg_step_queue.hpp)
 constexpr int32_t QT_SLOTS = 0xFFFF;      // slots of the tile
 constexpr int32_t QT_XLDS = 0x20000;      // the tile's state lives in LDS
 constexpr int32_t QT_LEAN = 0x40000;      // the lean LDS layout (QTile): what lets the state fit
@@ -1189,7 +1189,7 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_lean.hpp"
 #include "pcg_step_queue.hpp"
 #include "pcg_rollout_flat.hpp"
-// (also under hipRTC: a plan's second run-time compiled module instantiates the two closed-loop kernels, pcg_abi.hip jit_closed_loop)
+// (also under hipRTC: a plan's second run-time compiled module instantiates the two closed-loop kernels, pcg_abi_jit.hip jit_closed_loop)
 #include "pcg_rollout_policy.hpp"
 #include "pcg_rollout_actor.hpp"
 #ifndef __HIPCC_RTC__

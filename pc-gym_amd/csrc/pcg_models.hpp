@@ -1065,7 +1065,7 @@ struct Model<PCG_MODEL_OSCILLATORS> {
 
 // ---------------------------------------------------------------------------
 // PCG_MODEL_USER -- custom_model with an arbitrary right-hand side (pcgym.py:150-153: any object with
-// __call__(x, u) and info()).  Exists only inside a run-time compiled translation unit: pcg_abi.hip defines the sizes
+// __call__(x, u) and info()).  Exists only inside a run-time compiled translation unit: pcg_abi_jit.hip defines the sizes
 // as macros, splices the user's statements into pcg_user_rhs() and instantiates the general kernels for this model.
 // Parameters live in the 136-double constant block the affine custom model uses (DevConst::kp_big).
 // ---------------------------------------------------------------------------

@@ -5,7 +5,7 @@
 //
 // Flat parameter order (the contract of all five entry points).  Parameter j of a member, 0 <= j < n, runs layer by layer:
 // W[l] row-major (n_next x n_prev), then b[l]; n = sum_l rows_l (cols_l + 1).  Its place in the member's device block is
-// pack_policy's (pcg_abi.hip): header + offW[l] + r ld[l] + k, header + offb[l] + r.  No kernel here writes the header or a
+// pack_policy's (pcg_policy_pack.hpp): header + offW[l] + r ld[l] + k, header + offb[l] + r.  No kernel here writes the header or a
 // padding entry: they keep what pcg_policy_pop_create put there (zeros, so that padding units stay exact zeros).
 //
 // Search noise (RNG contract, purpose RNG_SEARCH = 0x500).  For member m (the population's own index),
@@ -31,7 +31,7 @@
 //   pop_set_flat_kernel
 // The summation order is fixed by the chunk size alone, never by the launch shape: the same bits for every grid.
 //
-// A float32 population (pcg_policy_pop_create_f32; blocks of pack_policy_f32's form) has siblings of the three kernels that touch
+// A float32 population (pcg_policy_pop_create_f32; blocks of pack_policy's float32 form) has siblings of the three kernels that touch
 // the blocks: pop_sample_kernel_f32, pop_get_flat_kernel_f32, pop_set_flat_kernel_f32.  Same flat order, same keys, same fp64
 // mean / std / theta; a parameter lives at a FLOAT offset, matrices with the rows of two consecutive units interleaved:
 //     W (l, r, k) at  HDR + offW[l] + ((r / 2) ld[l] + k) 2 + (r & 1),   b (l, r) at  HDR + offb[l] + r      (HDR in floats)
@@ -40,22 +40,14 @@
 // noise sum does not read the blocks: one kernel serves both kinds.
 #pragma once
 
+#include "pcg_policy_layout.hpp"  // PopLayout
+
 namespace pcg {
 
 // (RNG_SEARCH stands beside RNG_POLICY in pcg_rollout_actor.hpp)
 constexpr int POP_CHUNK = 64;            // members per partial sum of pcg_policy_pop_noise_dot (PCG_POP_CHUNK)
 constexpr int POP_BLOCK = 256;
 constexpr int POP_MAX_GRID_Y = 32768;    // rows of the grid; the kernels stride over members / chunks / rows beyond it
-
-// Where the flat parameters of a member live in its device block (offsets in ELEMENTS from the block's first byte, the header
-// included -- doubles, or floats for a float32 population): a few words that travel in the kernel arguments.
-struct PopLayout {
-  int32_t n;         // parameters per member
-  int32_t f32;       // element kind: 0 doubles, rows plain; 1 floats, the rows of two consecutive units interleaved
-  int32_t nl;        // layers (1..3)
-  int32_t start[4];  // flat index of layer l's first parameter; start[nl] = n
-  int32_t rows[3], cols[3], ld[3], offW[3], offb[3];
-};
 
 // offset (doubles, from the block's start) of flat parameter j, 0 <= j < L.n
 __device__ __forceinline__ int pop_param_offset(const PopLayout& L, int j) {
@@ -70,7 +62,7 @@ __device__ __forceinline__ int pop_param_offset(const PopLayout& L, int j) {
   return L.offW[l] + r * L.ld[l] + (local - r * cols);
 }
 
-// ... of a float32 population: offset in floats, pack_policy_f32's interleaved rows
+// ... of a float32 population: offset in floats, the float32 form's interleaved rows
 __device__ __forceinline__ int pop_param_offset_f32(const PopLayout& L, int j) {
   int l = 0;
   if (L.nl > 1 && j >= L.start[1]) l = 1;

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(FLAT_BLOCK, PCG_FLAT_WPE) void rollout_kernel_hot(c
   EnvPre<M> pre;
   DpLane<NX> L;
   bool drained = n_items <= 0;  // wave-uniform
-  const int every = A.q_tile > 0 ? A.q_tile : 1;  // the step boundaries run every that many iterations (host: pcg_abi.hip)
+  const int every = A.q_tile > 0 ? A.q_tile : 1;  // the step boundaries run every that many iterations (host: pcg_abi_step.hip)
   // every spin is bounded (max_steps bounds each env step): a logic error becomes a flagged result, not a hung GPU
   const long long cap64 = ((long long)c.max_steps + 8) * (long long)T * 4 + 64;
   for (long long iter = 0; iter < cap64 * 64; ++iter) {

@@ -16,28 +16,15 @@
 // layer four units at a time (four independent FMA chains), each unit consumed as soon as its activation is formed.
 // The register arrays are indexed with compile-time constants only; the loops over OUTPUT units run at run time (one code
 // body whatever the width), the loops over INPUT units are unrolled in blocks that a uniform branch skips past the layer's
-// width.  The host pads every matrix with zero rows / columns / biases to those block sizes (pack_policy, pcg_abi.hip), and
+// width.  The host pads every matrix with zero rows / columns / biases to those block sizes (pack_policy, pcg_policy_pack.hpp), and
 // tanh(0) = relu(0) = 0, so padding units are exact zeros.
 // No MFMA: v_mfma_f64_16x16x4_f64 over the wave's 64 envs needs the activations transposed through LDS between layers; the
 // measured case for it is the 2 x 64 policy.
 #pragma once
 
+#include "pcg_policy_layout.hpp"  // PolicyDev and the block sizes POL_*
+
 namespace pcg {
-
-constexpr int POL_MAX_W = 64;   // widest hidden layer
-constexpr int POL_IB = 4;       // input-side block of the first layer (columns padded to a multiple)
-constexpr int POL_HB = 8;       // hidden-side block: rows of a hidden layer fed by the input, columns of a layer fed by h1
-constexpr int POL_SB = 4;       // units of the streamed second hidden layer formed together
-
-// Header of a policy's device block; the packed weights follow it (offsets in doubles from the end of the header).
-struct PolicyDev {
-  int32_t n_in, n_out, n_hidden, act, out_map;
-  int32_t w[2];
-  int32_t ld[3];      // padded row length of each layer's matrix
-  int32_t offW[3], offb[3];
-  double out_lo, out_hi;
-};
-static_assert(sizeof(PolicyDev) % 8 == 0, "the weights behind the header are doubles");
 
 struct PolicyArgs {
   const PCG_CONSTANT PolicyDev* P;
@@ -203,7 +190,7 @@ constexpr int policy_nin() {
 }
 
 // Closed-loop fused rollout.  Plans without constraint rows, per-env parameters or user expressions, lock-stepped, RK4 / CV8
-// (checked on the host: closed_loop_open, pcg_abi.hip).  Reads io->obs (the observation before step t0), writes what
+// (checked on the host: closed_loop_open, pcg_abi_policy.hip).  Reads io->obs (the observation before step t0), writes what
 // pcg_rollout writes plus the recorded policy outputs.
 // The loop is stated here and again in rollout_actor_kernel (pcg_rollout_actor.hpp), ON MEASUREMENT.  As one PCG_DEV
 // function template that both __global__ functions call, with what happens between two steps as a template argument, it

@@ -28,12 +28,11 @@
 // collectors step instead.  No LDS, no mutable plan or policy state: capture-safe, usable from several streams.
 #pragma once
 
+#include "pcg_policy_layout.hpp"  // POL32_OR
+
 namespace pcg {
 
 typedef float pol_f2 __attribute__((ext_vector_type(2)));
-
-constexpr int POL32_OR = (PCG_MAX_NA + 1) / 2 * 2;  // rows of the output matrix (an even number: units come in pairs)
-static_assert(POL_IB % 2 == 0 && POL_HB % 2 == 0 && POL_SB % 2 == 0 && POL32_OR % 2 == 0, "float32 policy: units come in pairs");
 
 PCG_DEV float pol_act32(float v, int act) {
   if (act == PCG_ACT_TANH) return tanhf(v);

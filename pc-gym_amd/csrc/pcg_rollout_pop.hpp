@@ -5,7 +5,7 @@
 // hyper-parameter sweeps ask for.  Without it a caller with P policies makes P launches of a few workgroups each, or steps
 // with a batched matmul in torch.
 //
-// A population is P device blocks of ONE shape at a fixed byte stride, each exactly what pack_policy (pcg_abi.hip) writes for
+// A population is P device blocks of ONE shape at a fixed byte stride, each exactly what pack_policy (pcg_policy_pack.hpp) writes for
 // a pcg_policy: policy_eval (pcg_rollout_policy.hpp) reads a member unchanged.  The kernel is rollout_policy_kernel's loop
 // restated -- restated, not shared, for the reason measured in profiles/r9/closed_loop_refactor.txt and given above that
 // kernel -- with two differences:
@@ -18,7 +18,7 @@
 //            nor re-reads T x B rewards:   J = J + disc * r;  disc = disc * gamma   from J = 0, disc = 1, every operation
 //            rounded on its own (contraction off for the two statements, as in pcg_gae.hpp).  That defines the bits.
 //
-// A float32 population (pcg_policy_pop_create_f32) is P blocks of pack_policy_f32's form, and rollout_pop_policy_kernel_f32
+// A float32 population (pcg_policy_pop_create_f32) is P blocks of pack_policy's float32 form, and rollout_pop_policy_kernel_f32
 // below is the same loop with pcg_rollout_policy_f32.hpp's evaluator: the network in float32, the env, J and disc in fp64.
 //
 // Out of scope: stochastic actors over a population, plans with constraint rows, with per-env parameters and with run-time
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(BLOCK, M::NX <= 10 ? PCG_POL_WPE : 1) void rollout_
 }
 
 // The same loop with the member's network evaluated in float32: policy_raw_f32 + policy_map_f32 (pcg_rollout_policy_f32.hpp)
-// in place of policy_eval, on a block of pack_policy_f32's form.  A float32 block is half the bytes a wave streams per step.
+// in place of policy_eval, on a block of pack_policy's float32 form.  A float32 block is half the bytes a wave streams per step.
 // Waves per SIMD asked for the models of up to ten states: rollout_policy_kernel_f32's two, for the reason given above that
 // kernel -- the bitwise replay of the recorded actions through the open-loop general kernel is the bar
 // (tests/test_gpu_pop_f32.py), and a register budget is changed HERE when an instantiation misses it.

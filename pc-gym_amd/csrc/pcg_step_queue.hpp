@@ -688,7 +688,7 @@ struct QLayout {
 // wpe()).  The Rosenbrock loop wants ~316 registers: at two waves per SIMD it spills 34 scratch accesses per attempt, at
 // one (256 VGPRs + AGPRs) none -- the instantiation for launches that fit ONE tile per CU (me10 at B = 2^18: 0.361 -> 0.337 ms)
 // QB: threads per workgroup.  256 = one wave per SIMD and workgroup, as many workgroups per CU as the registers allow;
-// 512 = the two waves of every SIMD belong to ONE workgroup and share ONE tile of twice the size (see pcg_abi.hip:
+// 512 = the two waves of every SIMD belong to ONE workgroup and share ONE tile of twice the size (see pcg_abi_step.hip:
 // queue launch geometry): a pool twice as deep for the same lanes, and no wave left alone behind its SIMD-mate's tile.
 // FIX: the fix-up launch of a guarded plan (its own instantiation: the launches of the adaptive plans carry none of it)
 template <class M, bool PER_ENV_T, bool EXTRAS, int INTEG = PCG_INT_DOPRI5, int WAVES = 0, int QB = QBLOCK, bool FIX = false>
@@ -698,7 +698,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
   CDevConst& c = *A.C;
   constexpr int NX = M::NX, NA = M::NA, NDM = M::NDM, NU = NA + NDM;
   const int T = A.q_tile & QT_SLOTS;
-  constexpr bool fix = FIX;  // fix-up launch of a guarded plan (pcg_abi.hip): only the envs the first launch marked
+  constexpr bool fix = FIX;  // fix-up launch of a guarded plan (pcg_abi_step.hip): only the envs the first launch marked
   static_assert(QSORT == (1 << QSLOT_BITS), "slot index field");
   const bool lean = (A.q_tile & QT_LEAN) != 0;  // the lean LDS layout (QTile; host: it is what lets the state fit)
   const int nus = lean ? NA + c.nd : NU;
@@ -802,7 +802,7 @@ __global__ __launch_bounds__(QB, WAVES > 0 ? WAVES : wpe(M::NX, PCG_INT_DOPRI5, 
       // stability-limited part (the model's rate x dt) + the initial transient's share (ln of the scaled |f(x0)|,
       // already computed for the initial step size).  A least-squares fit on BASELINE configs[2] puts the weight at
       // 33 (correlation with the measured step counts 0.84 -> 0.96, list-scheduling efficiency of independent lanes
-      // 0.836 -> 0.862); lock-stepped waves prefer less: measured optimum ~20 (pcg_abi.hip, profiles/r2/queue_w_sweep.txt)
+      // 0.836 -> 0.862); lock-stepped waves prefer less: measured optimum ~20 (pcg_abi_step.hip, profiles/r2/queue_w_sweep.txt)
       if constexpr (is_ros_pair(INTEG))  // fitted attempts per env step of the (fourth-order) Rosenbrock pair (pcg_models.hpp)
         key = M::cost_key_ros(kp, pre.u) + A.q_w * __builtin_logf(__builtin_fmaxf((float)d1, 1.0f));
       else if constexpr (has_cost_key<M>::value)

@@ -111,7 +111,7 @@ def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
     fused_ok = (not s.ncon and (not s.nunc or s.integrator in ("rk4", "dopri5")) and (s.integrator not in ("rodas3", "rodas4", "rodas5", "tsit5") or (s.integrator in ("rodas4", "rodas5") and s.model.name == "multistage_extraction"))
                 and (s.user_rhs_src is None or s.integrator in ("rk4", "cv8", "dopri5"))
                 # a plan with user expressions runs from its run-time compiled module, which carries a rollout kernel only
-                # for the register-only explicit schemes (pcg_abi.hip: jit_kernels): the Rosenbrock pairs step instead
+                # for the register-only explicit schemes (pcg_abi_jit.hip: jit_kernels): the Rosenbrock pairs step instead
                 and not ((s.user_reward_src or s.user_cons_src) and s.integrator in ("rodas3", "rodas4", "rodas5"))
                 and (s.integrator in ("rk4", "cv8") or s.nx <= 10))
     if actions is not None:

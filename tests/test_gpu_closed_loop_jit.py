@@ -1,7 +1,7 @@
 """GPU: the fused closed-loop rollouts (pcg_rollout_policy, pcg_rollout_actor) on plans with run-time compiled code -- a
 user model (PCG_MODEL_USER) or a reward expression on a built-in model.  Such a plan runs rollout_policy_kernel /
 rollout_actor_kernel from a SECOND run-time compiled module, built at the plan's first closed-loop call or by
-pcg_plan_prepare_closed_loop (pcg_abi.hip: jit_closed_loop), never at pcg_plan_create.
+pcg_plan_prepare_closed_loop (pcg_abi_jit.hip: jit_closed_loop), never at pcg_plan_create.
 
 Every comparison is teacher-forced, as in test_gpu_policy_rollout.py: the policy half is checked on the kernel's own
 recorded observations, the env half from the recorded actions, so closed-loop amplification stays out of the tolerances.

@@ -1,4 +1,4 @@
-"""The order in which the six fused closed-loop entry points refuse bad arguments (pcg_abi.hip: closed_loop_open, the head's
+"""The order in which the six fused closed-loop entry points refuse bad arguments (pcg_abi_policy.hip: closed_loop_open, the head's
 own function, closed_loop_launch -- read top to bottom):
 
    1  plan and buffers (fill_args)                          PLAN / NULL / DIM

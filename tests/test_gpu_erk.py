@@ -303,7 +303,7 @@ def test_full_size_default_plans_of_four_tank_and_cryst():
 @pytest.mark.parametrize("kw", [{}, dict(per_env_t=True, auto_reset=True), dict(auto_reset=True)])
 def test_guarded_plans_two_launch_form_is_the_single_launch_bit_for_bit(integrator, kw, monkeypatch):
     """Batches that fill the chip run a guarded plan as two launches -- the general kernel marks the envs its guard does not
-    trust, the work-queue kernel of the adaptive pair integrates exactly those (pcg_abi.hip) -- where smaller ones keep the
+    trust, the work-queue kernel of the adaptive pair integrates exactly those (pcg_abi_step.hip) -- where smaller ones keep the
     fallback inside the first kernel (the form the oracle tests above pin).  The arithmetic of an env is the same either way:
     on the ignition box, with observation noise and a constraint, both forms give the same bits in every output, every step,
     through episode ends (a plan created with PCG_NO_FIXUP=1 keeps the single launch at any size)."""

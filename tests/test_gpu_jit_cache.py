@@ -1,4 +1,4 @@
-"""GPU: the disk cache of the run-time compiled kernels (pcg_abi.hip: jit_kernels) -- ADVICE r2.
+"""GPU: the disk cache of the run-time compiled kernels (pcg_abi_jit.hip: jit_kernels) -- ADVICE r2.
   * the key covers the CONTENT of the kernel headers (a header that changes without changing a struct size gets a new
     code object), not only the generated translation unit;
   * the directory is private (0700, owner-only files), a directory others can write is not used;

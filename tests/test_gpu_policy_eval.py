@@ -1,5 +1,5 @@
 """GPU: the in-kernel MLP evaluator (policy_raw / policy_map, pcg_rollout_policy.hpp; its packed weights: pack_policy,
-pcg_abi.hip) on the networks the closed-loop suites never feed it: ragged widths, ReLU, every output map, large arguments of
+pcg_policy_pack.hpp) on the networks the closed-loop suites never feed it: ragged widths, ReLU, every output map, large arguments of
 tanh, non-finite observations, an actor and a critic of different shapes.  Property checks only: no oracle, no golden file.
 
 How the evaluator is driven (helpers.tanh_k's trick): chosen inputs are written into env.obs_soa, one closed-loop call with

@@ -257,7 +257,7 @@ def test_unsupported_plans_are_refused_and_still_collect(what):
 
 @pytest.mark.parametrize("entry", ["policy", "actor"])
 def test_bad_arguments_are_refused_before_any_launch(entry):
-    """the argument checks both entry points share, by return code and in their order of precedence (pcg_abi.hip:
+    """the argument checks both entry points share, by return code and in their order of precedence (pcg_abi_policy.hip:
     closed_loop_open, the entry point's own checks, closed_loop_launch).  First a valid call as the positive control; then
     every bad call returns its code, leaves env.x, env.obs_soa and every output buffer as they were, and launches no
     closed-loop kernel.  Every call here is refused by host validation: nothing reaches the device."""

@@ -404,7 +404,7 @@ def test_queue_shapes(key, integ, B, pe):
     """the extraction cascade at the batch sizes that select: 512-thread workgroups (DOPRI5 from 229,376 envs), ONE
     workgroup per CU on the register-only instantiation (the Rosenbrock pairs between 65,536 and 300,000 envs) and two
     workgroups per CU beyond -- one env step of the full batch against the oracle, every env: these shapes place the envs
-    into tiles and sub-tiles (queue_shape, pcg_abi.hip), and a window would see a few of several hundred workgroups"""
+    into tiles and sub-tiles (queue_shape, pcg_abi_step.hip), and a window would see a few of several hundred workgroups"""
     import torch
     from oracle import oracle as O
 

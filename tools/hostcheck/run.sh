@@ -1,5 +1,6 @@
 #!/bin/bash
-# Host-side sanitizer runs of the Rosenbrock attempt templates (see ros_host_check.cpp).  No GPU, no HIP runtime.
+# Host-side sanitizer runs of the Rosenbrock attempt templates (see ros_host_check.cpp) and of the device-free host code
+# (see host_code_check.cpp).  No GPU, no HIP runtime: for a CPU machine.
 #   tools/hostcheck/run.sh > profiles/r6/ros_host_check.txt
 set -u
 cd "$(dirname "$0")"
@@ -18,3 +19,7 @@ g++ -std=c++17 -O1 -g -ffp-contract=off -DPCG_ROS_ROLLED_ABOVE=12 -fsanitize=add
 echo "# (4) g++ -O2 -Wall -Wextra -Wuninitialized -Wmaybe-uninitialized -Warray-bounds=2: diagnostics in the product headers"
 g++ -std=c++17 -O2 -Wall -Wextra -Wuninitialized -Wmaybe-uninitialized -Warray-bounds=2 $W -Wno-unused-parameter -Wno-unused-variable -Wno-unused-function ros_host_check.cpp -o /tmp/ros_host_warn 2>&1 | grep -E "warning" | grep -E "uninit|array-bounds|overflow" | sort | uniq -c | head -20
 echo "(end of diagnostics)"
+echo "# (5) the device-free host code (host_code_check.cpp: policy block packers, run-time compilation disk cache), g++ -O1 as in (1)"
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined host_code_check.cpp -o /tmp/host_code_asan && /tmp/host_code_asan; echo "exit $?"
+echo "# (6) ... clang++ -O3 as in (2)"
+$CLANG -std=c++17 -O3 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined host_code_check.cpp -o /tmp/host_code_asan_clang && /tmp/host_code_asan_clang; echo "exit $?"
