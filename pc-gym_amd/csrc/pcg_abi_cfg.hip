@@ -84,6 +84,10 @@ int build_devconst(const pcg_env_cfg* c, DevConst* d, int* cfg_nu_out) {
       d->a_act_lo[i] = c->a_act_low[i]; d->a_act_hi[i] = c->a_act_high[i]; d->a_0[i] = c->a_0[i];
     }
   }
+  // the lean step's action map: the half widths folded here, for the whole plan or not at all (amap_fold, pcg_kernels.hpp)
+  d->a_mode = norm_a ? PCG_AMAP_FOLDED : PCG_AMAP_NONE;
+  for (int i = 0; i < na; ++i)
+    if (norm_a && !amap_fold(d->a_lo[i], d->a_hi[i], &d->a_w[i])) d->a_mode = PCG_AMAP_EXACT;
   for (int i = 0; i < nobs; ++i) {
     const bool masked = (i < nx) && c->obs_mask && !c->obs_mask[i];
     if (masked) {

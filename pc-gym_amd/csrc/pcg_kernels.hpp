@@ -85,6 +85,21 @@ constexpr int CON_W = PCG_MAX_NX + PCG_MAX_NSP + PCG_MAX_NDM + KNU; // padded co
 struct OMap {
   double lo, sc, off;      // obs = (o - lo) * sc + off          (pcgym.py:483-498; mask -> sc=off=0)
 };
+// DevConst::a_mode, how env_step_lean maps its action: not at all (normalise_a off), (a + 1) * a_w + a_lo with the half
+// width from the host, or through action_map() where that fold would not be exact (amap_fold, below).
+enum { PCG_AMAP_NONE = 0, PCG_AMAP_FOLDED = 1, PCG_AMAP_EXACT = 2 };
+// With p = a + 1, d = hi - lo and w = d 0.5:  fl(fl(p d) 0.5) == fl(p w) bit for bit, because a scaling by a power of two
+// commutes with rounding as long as nothing on the way is subnormal or overflows.  A non-zero p = fl(a + 1) is at least
+// 2^-53 in magnitude, so with d finite and |w| >= 2^-969 (or d == 0) p d 0.5 is normal for every action; an infinite or NaN
+// p gives the same infinity or NaN both ways.  What remains is overflow: |p d| >= 2^1024 is infinite in action_map() and
+// may be finite here -- actions beyond 2^1023 / |d|, past anything a normalised policy emits.
+// Where the rule fails (w subnormal: it may have lost d's last bit, and the product is rounded twice in one form and once
+// in the other; d infinite) the plan keeps action_map().
+inline bool amap_fold(double lo, double hi, double* w) {
+  const double d = hi - lo, h = d * 0.5;
+  *w = h;
+  return __builtin_fabs(d) < __builtin_inf() && (d == 0.0 || __builtin_fabs(h) >= 0x1p-969);
+}
 struct DevConst {
   double dt, h, rtol, atol;
   double dt_edge, h_floor;            // dt (1 - 1e-14) and 1e-13 dt of the DOPRI5 loop, folded on the host
@@ -93,8 +108,10 @@ struct DevConst {
   uint32_t flags;
   int32_t nx, na, ndm, nd, nsp, nsp_obs, ncon, nrew, N, substeps, max_steps, nobs, has_x0_unc, nunc;
   int32_t sp_index[PCG_MAX_NSP], d_slot[PCG_MAX_NDM];
+  int32_t a_mode;                     // env_step_lean's action map (PCG_AMAP_*, above); sits in what was padding
   double kp[16];                      // model KP (pcg_models.hpp) of the five built-in models
   double a_lo[PCG_MAX_NA], a_hi[PCG_MAX_NA];  // a_space: action_map() (pcgym.py:372-379)
+  double a_w[PCG_MAX_NA];             // (a_hi - a_lo) * 0.5, folded on the host (build_devconst; PCG_AMAP_FOLDED only)
   double r_scale[PCG_MAX_NX];
   double d_default[PCG_MAX_NDM];
   OMap omap[PCG_MAX_NOBS];

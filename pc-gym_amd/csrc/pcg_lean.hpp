@@ -33,6 +33,20 @@ PCG_DEV Pack<W> pick(const Pack<W> (&v)[NX], int idx) {
   return r;
 }
 
+// One set-point's term of the reward, r + (-(dd dd)) r_scale with dd = x[idx] - spn, for a wave-uniform idx within [0, NX)
+// (build_devconst refuses any other): the row is chosen by scalar branches, one arm taken and the last one without a test,
+// where pick() spends 2 W selects per state on the vector unit.  No arm writes r ahead of its branch.
+template <int NX, int W, int I = 0>
+PCG_DEV void reward_row(const Pack<W> (&x)[NX], int idx, double spn, double r_scale, Pack<W>& r) {
+  if (I == NX - 1 || idx == I) {
+    const Pack<W> dd = x[I] - spn;
+    r = r + (-(dd * dd)) * r_scale;
+    asm volatile("");  // keep it a (scalar) branch
+  } else {
+    if constexpr (I + 1 < NX) reward_row<NX, W, I + 1>(x, idx, spn, r_scale, r);
+  }
+}
+
 template <class M, int W>
 struct LeanOut {
   Pack<W> ox[M::NX];
@@ -48,25 +62,58 @@ struct LeanOut {
 // +9 % time), so everything wave-uniform is gone from the vector unit -- the SP / disturbance slots of step t come
 // finished from the host (LeanStep, scalar loads), h/2 and h/6 too, and the normalised-action branch is a scalar branch
 // instead of both values and a select.
+// Round 23 took what was left of it (profiles/r23/lean_trim.txt): the set-point's state row is chosen by a scalar branch, the
+// action box's half width comes from the host, and the action map is a function of its own, lean_input, so that the chained
+// kernel can apply it where the action rows land.  step_chain_kernel<cstr,2> executes 324.8 vector instructions per wave
+// and step (SQ_INSTS_VALU; 344.8 before), 306 of them in the RK4 stage loop.  PCG_LEAN_TRIM (bits, for the A/B builds of
+// that profile) switches each back: 1 the reward row, 2 the action map, 4 step_chain_kernel's action hand-over, 8 the
+// uniform store flags.
+#ifndef PCG_LEAN_TRIM
+#define PCG_LEAN_TRIM 15
+#endif
+
+// physical action u[0..NA) of the lean step (pcgym.py:371-375): DevConst::a_mode says how, one scalar branch
+template <class M, int W>
+PCG_DEV void lean_input(CDevConst& c, const Pack<W> (&a_in)[M::NA], Pack<W> (&u)[M::NA]) {
+#pragma clang fp contract(off)
+  constexpr int NA = M::NA;
+  const int na = M::DYNAMIC ? c.na : NA;
+#if PCG_LEAN_TRIM & 2
+  int32_t mode = c.a_mode;
+  asm volatile("" : "+s"(mode));  // one scalar register, and every arm writes u itself: scalar branches, no copy ahead of them
+  if (mode == PCG_AMAP_FOLDED) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+#pragma unroll
+      for (int j = 0; j < W; ++j) u[i].v[j] = (i < na) ? (a_in[i].v[j] + 1.0) * c.a_w[i] + c.a_lo[i] : 0.0;
+    asm volatile("");  // keep it a (scalar) branch
+  } else if (mode == PCG_AMAP_EXACT) {
+#else
+  if (c.flags & PCG_F_NORMALISE_A) {
+#endif
+#pragma unroll
+    for (int i = 0; i < NA; ++i) u[i] = (i < na) ? action_map(a_in[i], c.a_lo[i], c.a_hi[i], true, false) : Pack<W>(0.0);
+    asm volatile("");  // keep it a (scalar) branch
+  } else {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) u[i] = (i < na) ? a_in[i] : Pack<W>(0.0);
+    asm volatile("");
+  }
+}
+
+// the step from the physical action on
 template <class M, int W, int INTEG = PCG_INT_RK4>
-PCG_DEV void env_step_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, int t,
-                           const Pack<W> (&a_in)[M::NA], Pack<W> (&x)[M::NX], LeanOut<M, W>& out) {
+PCG_DEV void env_step_lean_u(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, int t,
+                             const Pack<W> (&ua)[M::NA], Pack<W> (&x)[M::NX], LeanOut<M, W>& out) {
   constexpr int NX = M::NX, NA = M::NA, NDM = M::NDM;
   using R = Pack<W>;
   const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
   const int N = c.N, nsp = c.nsp;
   typename M::CKP& kp = model_kp<M>(c);
-  // action map (pcgym.py:371-375) and held disturbance inputs (pcgym.py:386-404)
+  // the action and the held disturbance inputs (pcgym.py:386-404)
   R u[NA + NDM];
 #pragma unroll
-  for (int i = 0; i < NA; ++i) u[i] = (i < na) ? a_in[i] : R(0.0);
-  if (c.flags & PCG_F_NORMALISE_A) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-      if (i < na) u[i] = action_map(a_in[i], c.a_lo[i], c.a_hi[i], true, false);
-    asm volatile("");  // keep it a (scalar) branch
-  }
+  for (int i = 0; i < NA; ++i) u[i] = ua[i];
 #pragma unroll
   for (int j = 0; j < NDM; ++j) u[NA + j] = R(L.ud[j]);
   // integrate over [0,dt] with the input held (integrator.py:163-182)
@@ -82,14 +129,28 @@ PCG_DEV void env_step_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT L
 #pragma unroll
   for (int k = 0; k < PCG_MAX_NSP; ++k)
     if (k < nsp) {
+#if PCG_LEAN_TRIM & 1
+      int32_t idx = c.sp_index[k];
+      asm volatile("" : "+s"(idx));
+      reward_row<NX, W>(x, idx, L.spn[k], c.r_scale[k], r);
+#else
       const R dd = pick<NX, W>(x, c.sp_index[k]) - L.spn[k];
       r = r + (-(dd * dd)) * c.r_scale[k];
+#endif
     }
   out.rew = r;
   out.done = (t + 1 == N - 1);  // pcgym.py:448-449
 #pragma unroll
   for (int i = 0; i < NX; ++i)
     if (i < nx) out.ox[i] = (x[i] - c.omap[i].lo) * c.omap[i].sc + c.omap[i].off;
+}
+
+template <class M, int W, int INTEG = PCG_INT_RK4>
+PCG_DEV void env_step_lean(const StepArgs& A, CDevConst& c, const PCG_CONSTANT LeanStep& L, int t,
+                           const Pack<W> (&a_in)[M::NA], Pack<W> (&x)[M::NX], LeanOut<M, W>& out) {
+  Pack<W> ua[M::NA];
+  lean_input<M, W>(c, a_in, ua);
+  env_step_lean_u<M, W, INTEG>(A, c, L, t, ua, x, out);
 }
 
 template <int EPL>
@@ -152,6 +213,16 @@ struct LaneIdx {
 // the EPL values of a lane into one row (16 bytes when EPL == 2), non-temporal on request
 template <int EPL>
 PCG_DEV void put(double* p, const double (&v)[EPL], bool nt) {
+  // A flag that is not a constant goes through a scalar register first, so that each store tests a word of its own.  One
+  // boolean shared by the stores of a tile lives as a lane mask, and the branches between them had the compiler rebuild its
+  // negation on the vector unit (v_cndmask_b32 0, 1 + v_cmp_ne_u32, six pairs in step_chain_kernel<cstr,2>).
+#if PCG_LEAN_TRIM & 8
+  if (!__builtin_constant_p(nt)) {
+    int32_t w = nt;
+    asm volatile("" : "+s"(w));
+    nt = w != 0;
+  }
+#endif
   if (nt) Vec<EPL>::store_nt(p, v);
   else *reinterpret_cast<typename Vec<EPL>::T*>(p) = Vec<EPL>::make(v);
 }
@@ -574,6 +645,20 @@ __global__ __launch_bounds__(BLOCK, chain_wpe(M::NX, EPL)) void step_chain_kerne
   unpack<NX, EPL>(xv, nx, xs);
   const Rows obs{A.obs, Bs, nt};
   for (int s0 = 0; s0 < n; s0 += D) {
+    // The group's rows are consumed where they landed: the action map runs here, ahead of the next group's fetch, and its
+    // results are the registers the D steps hold.  (Unpacked rows held across the fetch instead are a copy of every row
+    // out of the registers the fetch is about to overwrite, and one back on the path without a fetch.)
+#if PCG_LEAN_TRIM & 4
+    Pack<EPL> ua[D][NA];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) land(an[d][i]);
+      Pack<EPL> as[NA];
+      unpack<NA, EPL>(an[d], na, as);
+      lean_input<M, EPL>(c, as, ua[d]);
+    }
+#else
     Pack<EPL> as[D][NA];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -581,6 +666,7 @@ __global__ __launch_bounds__(BLOCK, chain_wpe(M::NX, EPL)) void step_chain_kerne
       for (int i = 0; i < NA; ++i) land(an[d][i]);
       unpack<NA, EPL>(an[d], na, as[d]);
     }
+#endif
     asm volatile("" ::: "memory");
     if (s0 + D < n) fetch(s0 + D);
     asm volatile("" ::: "memory");
@@ -593,7 +679,11 @@ __global__ __launch_bounds__(BLOCK, chain_wpe(M::NX, EPL)) void step_chain_kerne
         int32_t held = cs[s].held;
         asm volatile("" : "+s"(held));  // (its two tests stay scalar branches, as in store_lean)
         LeanOut<M, EPL> out;
+#if PCG_LEAN_TRIM & 4
+        env_step_lean_u<M, EPL>(A, c, L, t, ua[d], xs, out);
+#else
         env_step_lean<M, EPL>(A, c, L, t, as[d], xs, out);
+#endif
         if (s + 1 < n) {
           put_obs_rows<M, EPL>(obs, at, nx, c.nsp_obs, c.nd, out.ox, L.osp, L.od, (held & 1) != 0);
         } else {  // the last step: the state goes back in place, row by row ahead of its observation row
