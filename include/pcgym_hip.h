@@ -762,12 +762,45 @@ PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
  * PCG_E_DIM unless (env_offset + B - 1) / envs_per_policy < P (B need not be a multiple of envs_per_policy); PCG_E_VALUE
  * for a gamma that is not finite or outside [0, 1]; then T / t0 / buffers / strides as in pcg_rollout_policy.
  * Reads the plan and the population and writes neither: no lazy allocation, no memset -- safe under stream capture.
- * Not here: stochastic actors over a population, plans with constraint rows or per-env parameters. */
+ * Not here: stochastic actors over a population, plans with constraint rows; plans with per-env parameters take
+ * pcg_rollout_policy_pop_unc below. */
 PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
                                    int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
                                    double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                                    int64_t rew_step_stride, int32_t record_next_action, double gamma, double* ret_out,
                                    uint64_t seed, void* stream);
+/* pcg_rollout_policy_pop on plans WITH per-env parameters (additive under ABI 16; kernels: csrc/pcg_rollout_pop_unc.hpp): a
+ * population searched or compared over a DISTRIBUTION of plants -- every env of a member's slice integrates with its own
+ * model parameters, sampled at reset (nunc > 0, the reference's domain randomisation).  Argument list and meaning, member
+ * selection (the global env index), the recurrence of ret_out and the choice of the kernel by the population's dtype are those
+ * of pcg_rollout_policy_pop; what per-env parameters change is what pcg_rollout_policy_unc says: the observation carries nunc
+ * more slots, [x | SP | d | unc], which the members read (n_in == Nobs of the plan, the parameter slots included) and the
+ * rows of obs_seq and the final io->obs carry, and io->p_unc [nunc][B] is read and never written.  A float32 population is
+ * evaluated in float32 on that wider input; the env, J and disc stay fp64.
+ * Numerical contract: each env computes what pcg_rollout_policy_unc computes with its member as the policy TO ROUNDING, not
+ * to the bit -- the two kernels are compiled separately and the compiler contracts the model's right-hand side in each on its
+ * own, as said of stepping above.  Against itself the call is bit for bit reproducible: the same bits for the same inputs;
+ * a call of T steps and chunked calls over the same steps return the same rows (ret_out: the stated recurrence over each
+ * chunk's rewards); a member's slice does not depend on the other members; shards reproduce the whole batch.
+ * Statuses, nothing launched or written on any of them, in this order:
+ *   1. plan, io and the handle as in pcg_rollout_policy_pop (PCG_E_PLAN for what is not a population of the plan's device);
+ *   2. PCG_E_UNSUPPORTED as in pcg_rollout_policy_unc: nunc == 0 (use pcg_rollout_policy_pop), ncon > 0, a plan with
+ *      run-time compiled code, io->t != NULL, an integrator other than PCG_INT_RK4, a model without the kernel (the affine
+ *      registry models);
+ *   3. PCG_E_DIM for members whose n_in / n_out are not the plan's Nobs / na (Nobs counts the parameter slots);
+ *   4. the slices and gamma exactly as in pcg_rollout_policy_pop: PCG_E_VALUE unless envs_per_policy and the env offset are
+ *      multiples of 64, PCG_E_DIM unless there is a member for every env, PCG_E_VALUE for a gamma outside [0, 1];
+ *   5. T / t0, NULL buffers -- io->p_unc == NULL among them, PCG_E_NULL exactly where pcg_rollout_policy_unc gives it -- and
+ *      strides.
+ * pcg_rollout_policy_pop keeps refusing plans with per-env parameters.
+ * Reads the plan, the population and io->p_unc and writes none of them; no allocation, no memset: safe under stream capture.
+ * Not here: plans with constraint rows, stochastic actors over a population, paired parameter draws across members,
+ * PCG_INT_CV8 and the adaptive integrators. */
+PCG_API int pcg_rollout_policy_pop_unc(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
+                                       int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                                       double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                       int64_t rew_step_stride, int32_t record_next_action, double gamma, double* ret_out,
+                                       uint64_t seed, void* stream);
 
 /* The weights of a population written and read ON the device (additive under ABI 16; kernels: csrc/pcg_pop_search.hpp):
  * what surrounds pcg_rollout_policy_pop in a derivative-free search loop -- sampling the members of a diagonal Gaussian,

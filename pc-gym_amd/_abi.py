@@ -227,6 +227,7 @@ EXPORTS = [
     "pcg_policy_pop_destroy",
     "pcg_policy_pop_size",
     "pcg_rollout_policy_pop",
+    "pcg_rollout_policy_pop_unc",
     "pcg_policy_pop_nparams",
     "pcg_policy_pop_sample",
     "pcg_policy_pop_noise_dot",
@@ -340,6 +341,8 @@ def declare(lib):
     lib.pcg_rollout_policy_pop.restype = C.c_int
     lib.pcg_rollout_policy_pop.argtypes = (lib.pcg_rollout_policy.argtypes[:3] + [C.c_int64] + lib.pcg_rollout_policy.argtypes[3:-2]
                                            + [C.c_double, vp] + lib.pcg_rollout_policy.argtypes[-2:])
+    lib.pcg_rollout_policy_pop_unc.restype = C.c_int
+    lib.pcg_rollout_policy_pop_unc.argtypes = list(lib.pcg_rollout_policy_pop.argtypes)
     # (the weights of a population on the device: sample, noise sum, flat vectors out and in)
     lib.pcg_policy_pop_nparams.restype = C.c_int
     lib.pcg_policy_pop_nparams.argtypes = [vp]

@@ -294,24 +294,55 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, c
   (void)hipLaunchKernel(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), argv, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
-// pcg_rollout_policy_pop's sibling of closed_loop_open, with its order of refusals: plan, buffers and handle; what the base
-// kind's kernels do not carry; run-time compiled code (the population kernel is ahead-of-time only); the members' sizes; then
-// what is the population's own -- the slices (whole waves per member, a member for every env) and gamma.
-static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, int64_t G, double gamma, StepArgs* a, const void** fn) {
+// pcg_rollout_policy_pop's and pcg_rollout_policy_pop_unc's sibling of closed_loop_open, with its order of refusals: plan,
+// buffers and handle; which plans the kind's kernels carry (the base kind's, without run-time compiled code: the population
+// kernels are ahead-of-time only; or, turned round, the unc kind's) and which kernel it is; the members' sizes; then what is the
+// population's own -- the slices (whole waves per member, a member for every env) and gamma.
+static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, ClosedLoopKind kind, int64_t G, double gamma, StepArgs* a,
+                    const void** fn) {
   PCG_TRY(fill_args(p, io, a));
   if (!q) return PCG_E_NULL;
   if (!pop_ok(q) || q->device != p->device) return PCG_E_PLAN;
   const DevConst& c = p->hc;
+  const Kernels& k = kernels(p->kid);
   const int ls = lean_scheme(p->integrator_id);
-  if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
-  if (p->jit_fn[0]) return PCG_E_UNSUPPORTED;
-  *fn = (const void*)(q->dtype == PCG_POL_F32 ? kernels(p->kid).roll_policy_pop_f32 : kernels(p->kid).roll_policy_pop)[ls];
+  const bool jit = p->jit_fn[0] != nullptr, f32 = q->dtype == PCG_POL_F32;
+  *fn = nullptr;
+  if (kind == ClosedLoopKind::unc) {
+    // parameters are required; no constraint rows, RK4 alone, and (the null entry) a model with kernels for them
+    if (c.nunc <= 0 || c.ncon > 0 || jit || io->t || p->integrator_id != PCG_INT_RK4) return PCG_E_UNSUPPORTED;
+    *fn = (const void*)(f32 ? k.roll_policy_pop_unc_f32 : k.roll_policy_pop_unc);
+  } else {
+    if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
+    if (jit) return PCG_E_UNSUPPORTED;
+    *fn = (const void*)(f32 ? k.roll_policy_pop_f32 : k.roll_policy_pop)[ls];
+  }
   if (!*fn) return PCG_E_UNSUPPORTED;
   if (q->shape.n_in != c.nobs || q->shape.n_out != c.na) return PCG_E_DIM;
   if (G < 64 || G % 64 != 0 || p->env_offset < 0 || p->env_offset % 64 != 0) return PCG_E_VALUE;
   if (io->B > 0 && (p->env_offset + io->B - 1) / G >= (int64_t)q->P) return PCG_E_DIM;
   if (!(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0)) return PCG_E_VALUE;
   return PCG_OK;
+}
+
+// the two population entry points: pop_open, the kernel argument, closed_loop_launch of the kind
+static int pop_rollout(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, ClosedLoopKind kind, int64_t G, int32_t t0, int32_t T,
+                       double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
+                       int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action, double gamma,
+                       double* ret_out, uint64_t seed, void* stream) {
+  StepArgs a;
+  const void* fn;
+  PCG_TRY(pop_open(p, io, q, kind, G, gamma, &a, &fn));
+  PopArgs pa;
+  pa.blocks = (const PCG_CONSTANT char*)q->dP;
+  pa.stride = (int64_t)(sizeof(double) * q->blob_doubles);
+  pa.G = G;
+  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
+  pa.record_next = record_next_action ? 1 : 0;
+  pa.gamma = gamma;
+  pa.ret_out = ret_out;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  return closed_loop_launch(p, io, a, fn, kind, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, PCG_OK, stream);
 }
 
 // two envs per lane with 16-byte accesses (2-byte for the flags): the rule of the lean kernels' tile I/O (step_lean, rollout_lean) --
@@ -533,19 +564,16 @@ int pcg_rollout_policy_pop(pcg_plan* p, const pcg_buffers* io, const pcg_policy_
                            int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
                            int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
                            int32_t record_next_action, double gamma, double* ret_out, uint64_t seed, void* stream) {
-  StepArgs a;
-  const void* fn;
-  PCG_TRY(pop_open(p, io, q, envs_per_policy, gamma, &a, &fn));
-  PopArgs pa;
-  pa.blocks = (const PCG_CONSTANT char*)q->dP;
-  pa.stride = (int64_t)(sizeof(double) * q->blob_doubles);
-  pa.G = envs_per_policy;
-  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
-  pa.record_next = record_next_action ? 1 : 0;
-  pa.gamma = gamma;
-  pa.ret_out = ret_out;
-  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
-  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::base, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, PCG_OK, stream);
+  return pop_rollout(p, io, q, ClosedLoopKind::base, envs_per_policy, t0, T, a_seq_out, a_step_stride, a_comp_stride, obs_seq,
+                     obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, record_next_action, gamma, ret_out, seed, stream);
+}
+
+int pcg_rollout_policy_pop_unc(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, int64_t envs_per_policy, int32_t t0,
+                               int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                               int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                               int32_t record_next_action, double gamma, double* ret_out, uint64_t seed, void* stream) {
+  return pop_rollout(p, io, q, ClosedLoopKind::unc, envs_per_policy, t0, T, a_seq_out, a_step_stride, a_comp_stride, obs_seq,
+                     obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, record_next_action, gamma, ret_out, seed, stream);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {

@@ -1218,6 +1218,8 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_unc.hpp"
 // (... nor the population forms of the fp64 and float32 policy kernels, which refuse run-time compiled plans)
 #include "pcg_rollout_pop.hpp"
+// (... nor the population forms on plans with per-env parameters)
+#include "pcg_rollout_pop_unc.hpp"
 #endif
 namespace pcg {
 
@@ -1289,6 +1291,7 @@ struct Kernels {
   ActFn roll_actor_unc;
   PopFn roll_policy_pop[2];          // roll_policy with one member of a policy population per slice of envs (pcg_rollout_pop.hpp)
   PopFn roll_policy_pop_f32[2];      // ... of a float32 population (pcg_policy_pop_create_f32)
+  PopFn roll_policy_pop_unc, roll_policy_pop_unc_f32;  // the population two on plans with per-env parameters (RK4; null for affine: pcg_rollout_pop_unc.hpp)
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1413,6 +1416,8 @@ Kernels make_kernels() {
     k.rollout_unc[PCG_INT_DOPRI5] = rollout_kernel<M, PCG_INT_DOPRI5, false, true>;
     k.roll_policy_unc = rollout_unc_policy_kernel<M>;
     k.roll_actor_unc = rollout_unc_actor_kernel<M>;
+    k.roll_policy_pop_unc = rollout_pop_unc_policy_kernel<M>;
+    k.roll_policy_pop_unc_f32 = rollout_pop_unc_policy_kernel_f32<M>;
   }
   if constexpr (M::FULL) {
     // DOPRI5 with the stage vectors in LDS (PCG_OPT_LDS_STAGES)

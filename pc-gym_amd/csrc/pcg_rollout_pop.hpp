@@ -21,8 +21,8 @@
 // A float32 population (pcg_policy_pop_create_f32) is P blocks of pack_policy's float32 form, and rollout_pop_policy_kernel_f32
 // below is the same loop with pcg_rollout_policy_f32.hpp's evaluator: the network in float32, the env, J and disc in fp64.
 //
-// Out of scope: stochastic actors over a population, plans with constraint rows, with per-env parameters and with run-time
-// compiled code (whose module does not carry these kernels: ahead-of-time only).
+// Out of scope: stochastic actors over a population, plans with constraint rows and with run-time compiled code (whose module
+// does not carry these kernels: ahead-of-time only).  Plans with per-env parameters: pcg_rollout_pop_unc.hpp.
 #pragma once
 
 namespace pcg {

@@ -468,17 +468,34 @@ class VecEnv:
         accumulated in the kernel: a search loop needs no T x B rewards.  ``envs_per_policy`` and the env offset must be
         multiples of 64 and the population must have a member for every env; plans the kernel does not take (constraints,
         per-env parameters, integrators other than rk4 / cv8, user models and expressions) raise PcgError."""
+        return self._rollout_population("rollout_policy_pop", pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions,
+                                        collect_returns, record_next_action)
+
+    def rollout_population_unc(self, pop, T, envs_per_policy, gamma=1.0, collect_obs=False, collect_rew=False, collect_actions=False,
+                               collect_returns=True, record_next_action=False):
+        """``rollout_population`` on a plan WITH per-env parameters (``pcg_rollout_policy_pop_unc``): the same launch and the
+        same dict; every env integrates with its own model parameters, and the observation rows (and the members' input) carry
+        the ``nunc`` parameter slots.  ``env.p_unc`` -- what the last reset sampled -- is read and left as it is.  Each env
+        computes what ``rollout_policy_unc`` with its member computes, to rounding and not to the bit (two separately compiled
+        kernels); against itself the call is bit for bit reproducible.  A float32 population is evaluated in float32.
+        Plans the kernel does not take (no per-env parameters, constraint rows, integrators other than rk4) raise PcgError."""
+        return self._rollout_population("rollout_policy_pop_unc", pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions,
+                                        collect_returns, record_next_action)
+
+    def _rollout_population(self, name, pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions, collect_returns,
+                            record_next_action):
+        """the two ``rollout_population*`` methods: output storage, the call ``pcg_<name>``, the step counter"""
         if self.per_env_t:
-            raise ValueError("rollout_population() is lock-stepped only")
+            raise ValueError(f"{name.replace('_policy_pop', '_population')}() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)
         R = T + (1 if record_next_action else 0)
         a_seq, obs_seq, rew_seq, ret = self._seq_buffers(
             ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew), ((B,), collect_returns))
         self._buf.d = None
-        _lib.check(self._lib.pcg_rollout_policy_pop(
+        _lib.check(getattr(self._lib, "pcg_" + name)(
             self._plan, self._bufp, pop.handle(dev), int(envs_per_policy), self.t, T,
             _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), float(gamma), _ptr(ret), self._episode_seed(), self._stream()), "pcg_rollout_policy_pop")
+            int(bool(record_next_action)), float(gamma), _ptr(ret), self._episode_seed(), self._stream()), "pcg_" + name)
         self.t += T
         return {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "ret": ret}
 

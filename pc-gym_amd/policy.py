@@ -693,6 +693,18 @@ def fused_pop_ok(spec, pop, envs_per_policy):
             and pop.n_in == spec.nobs and pop.n_out == spec.na and pop.validate() == 0)
 
 
+def fused_pop_unc_ok(spec, pop, envs_per_policy):
+    """the plans, populations and slices pcg_rollout_policy_pop_unc takes (include/pcgym_hip.h): those of
+    pcg_rollout_policy_unc -- per-env model parameters sampled at reset (``nunc``), RK4, no constraint rows, built-in plans
+    only -- with fused_pop_ok's populations and slices: members of the plan's sizes, whose input counts the parameter slots of
+    the observation, float64 or float32; slices of whole waves.  ``evaluate_population`` takes the call with
+    ``fused_unc=True``; its default route on such a plan stays the per-step loop."""
+    G = int(envs_per_policy)
+    return (isinstance(pop, PolicyPopulation) and spec.integrator == "rk4" and bool(spec.nunc) and not spec.ncon
+            and not _runtime_compiled(spec) and G >= 64 and G % 64 == 0
+            and pop.n_in == spec.nobs and pop.n_out == spec.na and pop.validate() == 0)
+
+
 def _runtime_compiled(spec):
     """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
     return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)

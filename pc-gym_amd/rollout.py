@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .policy import (fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_pop_ok,
-                     fused_unc_ok)
+                     fused_pop_unc_ok, fused_unc_ok)
 
 
 def _torch():
@@ -187,7 +187,7 @@ def collect_rollouts(env, policy=None, actions=None, fused_unc=False):
     return out
 
 
-def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
+def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None, fused_unc=False):
     """Score a :class:`~pcgym_amd.policy.PolicyPopulation` on a VecEnv: reset, one episode (N - 1 steps), env ``e`` driven by
     member ``(env.env_offset + e) // envs_per_policy`` -- the evaluation step of an evolution strategy, a cross-entropy search
     or a comparison of checkpoints under the same disturbances and noise.
@@ -199,10 +199,19 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
     offset is a multiple of 64; otherwise -- or with ``fused=False`` -- one ``env.step`` per step with the population's
     callable form and the kernel's recurrence in torch (``J = J + disc * rew; disc = disc * gamma``).  ``fused=True`` raises
     ValueError where the one launch is not possible.  A float32 population takes the same routes: the float32 kernel, or the
-    float32 callable per step."""
+    float32 callable per step.
+
+    fused_unc : True takes ``pcg_rollout_policy_pop_unc`` -- one launch as well -- on a built-in RK4 plan with per-env parameters,
+    and raises ValueError unless ``fused_pop_unc_ok(spec, pop, envs_per_policy)`` and the env offset is a multiple of 64, or
+    together with ``fused=False``.  It has to be asked for: by default such a plan keeps the per-step loop, whose results the
+    fused kernel matches to rounding and not to the bit (the two kernels are compiled separately)."""
     torch = _torch()
     s = env.spec
     B, G, off = env.B, int(envs_per_policy), int(env.env_offset)
+    if fused_unc and fused is False:
+        raise ValueError("fused_unc=True asks for the one launch that fused=False declines")
+    if fused_unc and not (fused_pop_unc_ok(s, pop, G) and off % 64 == 0):
+        raise ValueError("fused_unc: this plan / population / slice size does not qualify for pcg_rollout_policy_pop_unc (fused_pop_unc_ok)")
     if env.per_env_t:
         raise ValueError("evaluate_population needs a lock-stepped VecEnv")
     if pop.n_in != s.nobs or pop.n_out != s.na:
@@ -212,11 +221,13 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None):
     if not (0.0 <= float(gamma) <= 1.0):
         raise ValueError(f"gamma must be within [0, 1], not {gamma}")
     ok = fused_pop_ok(s, pop, G) and off % 64 == 0
-    if fused and not ok:
+    if fused and not ok and not fused_unc:
         raise ValueError("this plan / population / slice size does not qualify for the fused call (fused_pop_ok)")
     T = s.N - 1
     obs, _ = env.reset()
-    if ok and fused is not False:
+    if fused_unc:  # on request: the reset above sampled the parameters
+        ret = env.rollout_population_unc(pop, T, G, gamma=gamma)["ret"]
+    elif ok and fused is not False:
         ret = env.rollout_population(pop, T, G, gamma=gamma)["ret"]
     else:
         ret = torch.zeros(B, dtype=torch.float64, device=env.device)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A population of MLP policies in one fused closed-loop launch (pcg_rollout_policy_pop) against what a caller had before it.
 
-    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--dtype float32] [--out FILE]
+    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--dtype float32] [--per-env-params [--members 16,256,4096]] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s; one episode = 59 closed-loop steps).  All
 routes of a comparison alternate inside one process (`reps` rounds after one warm-up round); times are device-event times
@@ -23,6 +23,17 @@ is the median, the repeats are printed.
                                 recorded anywhere)
 
 --dtype float32 makes the populations and policies of parts 1 to 3 float32 ones as well.
+
+--per-env-params measures pcg_rollout_policy_pop_unc instead (and with --dtype float32 its float32 kernel): the workload is
+bench.py's cstr_unc (the headline's envs with UA and Caf ~ U(+-5 %) sampled per env at reset), P in --members distinct members
+on B / P envs each, all routes interleaved in one process:
+  new   the population call on the randomised plan
+  c     rollout_population with the same members (two inputs fewer) on the headline's envs WITHOUT uncertain parameters
+  d     rollout_policy_unc with ONE policy (member 0) on all envs (fp64 only: there is no float32 single-policy form)
+        -- these three with nothing recorded, from a copied-back start state --
+  eval  evaluate_population(fused_unc=True): reset, the one launch, the per-member scores
+  a     P times: reset of an env of B / P envs, rollout_policy_unc with member m (rewards recorded), their sum (fp64 only)
+  b     evaluate_population(fused=False): one env.step per step with the population's callable form in torch
 """
 import argparse
 import os
@@ -246,6 +257,87 @@ def part4(a, p, torch, VecEnv, PolicyPopulation, MLPPolicy):
     return lines
 
 
+def unc_rows(a, bench, torch, VecEnv, PolicyPopulation, evaluate_population):
+    p_unc, p_ref = bench.single_workload("cstr_unc")[1], bench.workload_params()
+    f64 = a.dtype == "float64"
+    lines = ["# --per-env-params: bench.py's cstr_unc (UA, Caf ~ U(+-5 %) per env), ms: new = pcg_rollout_policy_pop_unc, c = rollout_population "
+             "without uncertain parameters, d = rollout_policy_unc with ONE policy on all envs (nothing recorded in the three); eval = "
+             "evaluate_population(fused_unc=True), a = P x (reset, rollout_policy_unc, sum) on B / P envs, b = per-step route"]
+    kw = dict(activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
+    for name in a.shapes.split(","):
+        for P in [int(v) for v in a.members.split(",")]:
+            G = a.B // P
+            if G < 64 or G % 64:
+                continue
+            big, big2, plain, small = (VecEnv(dict(p_unc), n_envs=a.B, seed=1), VecEnv(dict(p_unc), n_envs=a.B, seed=1),
+                                       VecEnv(dict(p_ref), n_envs=a.B, seed=1), VecEnv(dict(p_unc), n_envs=G, seed=1))
+            spec, T = big.spec, big.spec.N - 1
+            assert spec.nunc == 2 and plain.spec.nobs == spec.nobs - 2 and plain.spec.N == spec.N
+            pop = PolicyPopulation(*member_arrays(spec, SHAPES[name], P), **kw)
+            pop_c = PolicyPopulation(*member_arrays(plain.spec, SHAPES[name], P), **kw)
+            members = [pop.member(m) for m in range(P if f64 else 0)]
+            for q in [pop, pop_c] + members:
+                q.handle(big.device)
+            starts = {}
+            for e in (big, plain):
+                e.reset()
+                starts[e] = (e.x.clone(), e.obs_soa.clone())
+
+            def restart(e):
+                e.x.copy_(starts[e][0]), e.obs_soa.copy_(starts[e][1])
+                e.t = 0
+
+            def f_new():
+                restart(big)
+                big.rollout_population_unc(pop, T, G, collect_returns=False)
+
+            def f_c():
+                restart(plain)
+                plain.rollout_population(pop_c, T, G, collect_returns=False)
+
+            def f_d():
+                restart(big)
+                big.rollout_policy_unc(members[0], T, collect_rew=False, collect_actions=False)
+
+            keep = {}
+
+            def f_eval():
+                keep["eval"] = evaluate_population(big, pop, G, gamma=1.0, fused_unc=True)["score"]
+
+            def f_a():
+                sc = []
+                for q in members:
+                    small.reset()
+                    sc.append(small.rollout_policy_unc(q, T, collect_actions=False)[2].sum(dim=0).mean())
+                keep["a"] = torch.stack(sc)
+
+            def f_b():
+                keep["b"] = evaluate_population(big2, pop, G, gamma=1.0, fused=False)["score"]
+
+            routes = {"new": f_new, "c": f_c, "eval": f_eval, "b": f_b}
+            if f64:
+                routes.update(d=f_d, a=f_a)
+            times = timed(torch, routes, a.reps)
+            med = {k: statistics.median(v) for k, v in times.items()}
+            gap = float((keep["eval"] - keep["b"]).abs().max())
+            row = (f"{name:7s} P={P:5d} G={G:6d}   new {med['new']:9.3f} ({med['new'] / T * 1e3:.1f} us per step)   c {med['c']:9.3f}   "
+                   f"new / c = {med['new'] / med['c']:.3f}")
+            if f64:
+                row += f"   d {med['d']:9.3f}   new / d = {med['new'] / med['d']:.3f}"
+            row += f"   |   eval {med['eval']:9.3f}   b {med['b']:9.3f}   b / eval = {med['b'] / med['eval']:.2f}"
+            if f64:
+                row += f"   a {med['a']:9.3f}   a / eval = {med['a'] / med['eval']:.2f}"
+            lines.append(row + f"   {a.B * T / med['eval'] / 1e-3:.3e} env-steps/s eval   max |score eval - b| {gap:.2e}")
+            lines.append("        repeats " + fmt(times))
+            for e in (big, big2, plain, small):
+                e.close()
+            for q in [pop, pop_c] + members:
+                q.close()
+            del big, big2, plain, small, members, pop, pop_c, starts
+            torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
@@ -253,6 +345,8 @@ def main():
     ap.add_argument("--shapes", default="affine,1x16,2x64")
     ap.add_argument("--parts", help="default: 1,2,3; under --dtype float32: 4")
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
+    ap.add_argument("--per-env-params", action="store_true", help="bench.py's cstr_unc: pcg_rollout_policy_pop_unc against what a caller had")
+    ap.add_argument("--members", default="16,256,4096", help="--per-env-params: the population sizes P")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -275,6 +369,10 @@ def main():
             with open(a.out, "w") as f:
                 f.write(text + "\n")
 
+    if a.per_env_params:
+        parts = []
+        lines += unc_rows(a, bench, torch, VecEnv, PolicyPopulation, evaluate_population)
+        flush()
     if "1" in parts:
         lines += part1(a, p, torch, VecEnv, PolicyPopulation, MLPPolicy)
         flush()
