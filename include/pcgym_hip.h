@@ -762,8 +762,8 @@ PCG_API int pcg_policy_pop_size(const pcg_policy_pop* pop);
  * PCG_E_DIM unless (env_offset + B - 1) / envs_per_policy < P (B need not be a multiple of envs_per_policy); PCG_E_VALUE
  * for a gamma that is not finite or outside [0, 1]; then T / t0 / buffers / strides as in pcg_rollout_policy.
  * Reads the plan and the population and writes neither: no lazy allocation, no memset -- safe under stream capture.
- * Not here: stochastic actors over a population, plans with constraint rows; plans with per-env parameters take
- * pcg_rollout_policy_pop_unc below. */
+ * Not here: stochastic actors over a population; plans with per-env parameters take pcg_rollout_policy_pop_unc and plans
+ * with constraint rows pcg_rollout_policy_pop_cons, both below (this call keeps refusing either plan). */
 PCG_API int pcg_rollout_policy_pop(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
                                    int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
                                    double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
@@ -801,6 +801,47 @@ PCG_API int pcg_rollout_policy_pop_unc(pcg_plan* plan, const pcg_buffers* io, co
                                        double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
                                        int64_t rew_step_stride, int32_t record_next_action, double gamma, double* ret_out,
                                        uint64_t seed, void* stream);
+/* pcg_rollout_policy_pop on plans WITH constraint rows (additive under ABI 16; kernels: csrc/pcg_rollout_pop_cons.hpp): the
+ * evaluation step of a CONSTRAINED derivative-free search -- "return minus lambda x violations", "reject members that ever
+ * violate" -- in one launch.  Member selection (the global env index), the recurrence of ret_out, the choice of the kernel by
+ * the population's dtype and every argument up to record_next_action are those of pcg_rollout_policy_pop; g_seq / viol_seq
+ * and their strides are those of pcg_rollout_policy_cons (rows [T][ncon][B]-like, step-major or component-major, flag bytes
+ * [T][B]-like), and so is what the call leaves in io: io->g / io->viol / io->done / io->obs / io->rew hold the last step,
+ * io->g_pre the pre-step check of a call that starts at counter 0 (written by no other call), and an env whose done flag is
+ * set mid-episode keeps stepping.  Two statistics are accumulated per env in registers beside the return, over THIS call's
+ * steps:
+ *     nviol_out [B] int32 (device) or NULL: the number of steps whose post-step flag "any row > 0" was set;
+ *     gmax_out  [B] (device) or NULL: the largest post-step row value over the steps and rows, from -inf with
+ *         gmax = (g > gmax) ? g : gmax          that statement defines the bits; a NaN row leaves gmax unchanged.
+ * The pre-step check at counter 0 counts in neither.  Every output may be NULL; the rows are summed regardless (the flag
+ * feeds the penalty, the box excess and `done`).
+ * Numerical contract: each env computes what pcg_rollout_policy_cons computes with its member as the policy, bit for bit --
+ * recorded actions, observations, rewards, rows, flags and the final io buffers (a float32 population: the member's float32
+ * network, which pcg_rollout_policy_cons itself does not take; its rows are the bits of stepping the recorded actions).  The
+ * rows are summed in the order pcg_step would use on the same buffers, as there.  nviol_out is the column sum of viol_seq,
+ * gmax_out the maximum of g_seq, ret_out the stated recurrence over rew_seq, whether or not those are recorded; chunked calls
+ * return the statistics of their own steps.
+ * Statuses, nothing launched or written on any of them, in this order:
+ *   1. plan, io and the handle as in pcg_rollout_policy_pop (PCG_E_PLAN for what is not a population of the plan's device);
+ *   2. PCG_E_UNSUPPORTED for ncon == 0 (use pcg_rollout_policy_pop);
+ *   3. PCG_E_UNSUPPORTED for nunc > 0, io->t != NULL, an integrator other than PCG_INT_RK4 / PCG_INT_CV8;
+ *   4. PCG_E_UNSUPPORTED for a plan with run-time compiled code (PCG_MODEL_USER, user_reward_src, a constraint expression:
+ *      no module carries these kernels -- nothing is compiled);
+ *   5. PCG_E_DIM for members whose n_in / n_out are not the plan's Nobs / na;
+ *   6. the slices and gamma exactly as in pcg_rollout_policy_pop: PCG_E_VALUE unless envs_per_policy and the env offset are
+ *      multiples of 64, PCG_E_DIM unless there is a member for every env, PCG_E_VALUE for a gamma outside [0, 1];
+ *   7. T / t0, NULL buffers and strides as in pcg_rollout_policy_cons (PCG_E_DIM for g_comp_stride < B, for
+ *      viol_step_stride < B while T > 1, for rows of g_seq that overlap).
+ * pcg_rollout_policy_pop keeps refusing plans with constraint rows.
+ * Reads the plan and the population and writes neither; no allocation, no memset: safe under stream capture.
+ * Not here: constraint expressions and user models, rows together with per-env parameters, stochastic actors over a
+ * population, cutting the return at the first violation (mask from viol_seq, or penalise through nviol_out). */
+PCG_API int pcg_rollout_policy_pop_cons(pcg_plan* plan, const pcg_buffers* io, const pcg_policy_pop* pop, int64_t envs_per_policy,
+                                        int32_t t0, int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride,
+                                        double* obs_seq, int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq,
+                                        int64_t rew_step_stride, int32_t record_next_action, double* g_seq, int64_t g_step_stride,
+                                        int64_t g_comp_stride, uint8_t* viol_seq, int64_t viol_step_stride, double gamma,
+                                        double* ret_out, int32_t* nviol_out, double* gmax_out, uint64_t seed, void* stream);
 
 /* The weights of a population written and read ON the device (additive under ABI 16; kernels: csrc/pcg_pop_search.hpp):
  * what surrounds pcg_rollout_policy_pop in a derivative-free search loop -- sampling the members of a diagonal Gaussian,

@@ -228,6 +228,7 @@ EXPORTS = [
     "pcg_policy_pop_size",
     "pcg_rollout_policy_pop",
     "pcg_rollout_policy_pop_unc",
+    "pcg_rollout_policy_pop_cons",
     "pcg_policy_pop_nparams",
     "pcg_policy_pop_sample",
     "pcg_policy_pop_noise_dot",
@@ -343,6 +344,11 @@ def declare(lib):
                                            + [C.c_double, vp] + lib.pcg_rollout_policy.argtypes[-2:])
     lib.pcg_rollout_policy_pop_unc.restype = C.c_int
     lib.pcg_rollout_policy_pop_unc.argtypes = list(lib.pcg_rollout_policy_pop.argtypes)
+    # (on plans with constraint rows: g_seq / strides / viol_seq / stride after record_next_action, nviol_out / gmax_out after ret_out)
+    lib.pcg_rollout_policy_pop_cons.restype = C.c_int
+    lib.pcg_rollout_policy_pop_cons.argtypes = (lib.pcg_rollout_policy_pop.argtypes[:-4] + [vp, C.c_int64, C.c_int64, vp, C.c_int64]
+                                                + lib.pcg_rollout_policy_pop.argtypes[-4:-2] + [vp, vp]
+                                                + lib.pcg_rollout_policy_pop.argtypes[-2:])
     # (the weights of a population on the device: sample, noise sum, flat vectors out and in)
     lib.pcg_policy_pop_nparams.restype = C.c_int
     lib.pcg_policy_pop_nparams.argtypes = [vp]

@@ -137,6 +137,7 @@ static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return 
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
 // (never asked for: pop_open refuses a plan with run-time compiled code, whose module does not carry the population kernels)
 static hipFunction_t jit_head_fn(const pcg_plan*, const PopArgs&) { return nullptr; }
+static hipFunction_t jit_head_fn(const pcg_plan*, const PopConsArgs&) { return nullptr; }
 
 // Plan, buffers and policy handle; then which plans the kind's kernels carry and which kernel it is (`actor`: the head); then
 // the policy's sizes.  *fn stays null for a plan with run-time compiled code, which has no ahead-of-time kernel:
@@ -294,9 +295,9 @@ static int closed_loop_launch(pcg_plan* p, const pcg_buffers* io, StepArgs& a, c
   (void)hipLaunchKernel(cov(fn), dim3(grid_for(io->B)), dim3(BLOCK), argv, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
-// pcg_rollout_policy_pop's and pcg_rollout_policy_pop_unc's sibling of closed_loop_open, with its order of refusals: plan,
-// buffers and handle; which plans the kind's kernels carry (the base kind's, without run-time compiled code: the population
-// kernels are ahead-of-time only; or, turned round, the unc kind's) and which kernel it is; the members' sizes; then what is the
+// The three population entry points' sibling of closed_loop_open, with its order of refusals: plan, buffers and handle; which
+// plans the kind's kernels carry (the base kind's, without run-time compiled code: the population kernels are ahead-of-time
+// only; or, turned round, the unc kind's or the cons kind's) and which kernel it is; the members' sizes; then what is the
 // population's own -- the slices (whole waves per member, a member for every env) and gamma.
 static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, ClosedLoopKind kind, int64_t G, double gamma, StepArgs* a,
                     const void** fn) {
@@ -312,6 +313,13 @@ static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q,
     // parameters are required; no constraint rows, RK4 alone, and (the null entry) a model with kernels for them
     if (c.nunc <= 0 || c.ncon > 0 || jit || io->t || p->integrator_id != PCG_INT_RK4) return PCG_E_UNSUPPORTED;
     *fn = (const void*)(f32 ? k.roll_policy_pop_unc_f32 : k.roll_policy_pop_unc);
+  } else if (kind == ClosedLoopKind::cons) {
+    // rows are required; then what the kernels are not built for (per-env parameters, per-env counters, another integrator);
+    // then run-time compiled code, a constraint expression among it (no closed-loop module carries these kernels)
+    if (c.ncon <= 0) return PCG_E_UNSUPPORTED;
+    if (c.nunc > 0 || io->t || ls < 0) return PCG_E_UNSUPPORTED;
+    if (jit) return PCG_E_UNSUPPORTED;
+    *fn = (const void*)(f32 ? k.roll_policy_pop_cons_f32 : k.roll_policy_pop_cons)[ls];
   } else {
     if (io->t || c.ncon > 0 || c.nunc > 0 || ls < 0) return PCG_E_UNSUPPORTED;
     if (jit) return PCG_E_UNSUPPORTED;
@@ -325,7 +333,20 @@ static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q,
   return PCG_OK;
 }
 
-// the two population entry points: pop_open, the kernel argument, closed_loop_launch of the kind
+// what PopArgs and PopConsArgs share
+template <class Args>
+static void pop_head(Args* pa, const pcg_policy_pop* q, int64_t G, double* a_out, int64_t ao_ss, int64_t ao_cs, int32_t record_next,
+                     double gamma, double* ret_out) {
+  pa->blocks = (const PCG_CONSTANT char*)q->dP;
+  pa->stride = (int64_t)(sizeof(double) * q->blob_doubles);
+  pa->G = G;
+  pa->a_out = a_out; pa->ao_ss = ao_ss; pa->ao_cs = ao_cs;
+  pa->record_next = record_next ? 1 : 0;
+  pa->gamma = gamma;
+  pa->ret_out = ret_out;
+}
+
+// the base and unc population entry points: pop_open, the kernel argument, closed_loop_launch of the kind
 static int pop_rollout(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, ClosedLoopKind kind, int64_t G, int32_t t0, int32_t T,
                        double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq, int64_t obs_step_stride,
                        int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride, int32_t record_next_action, double gamma,
@@ -334,13 +355,7 @@ static int pop_rollout(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop*
   const void* fn;
   PCG_TRY(pop_open(p, io, q, kind, G, gamma, &a, &fn));
   PopArgs pa;
-  pa.blocks = (const PCG_CONSTANT char*)q->dP;
-  pa.stride = (int64_t)(sizeof(double) * q->blob_doubles);
-  pa.G = G;
-  pa.a_out = a_seq_out; pa.ao_ss = a_step_stride; pa.ao_cs = a_comp_stride;
-  pa.record_next = record_next_action ? 1 : 0;
-  pa.gamma = gamma;
-  pa.ret_out = ret_out;
+  pop_head(&pa, q, G, a_seq_out, a_step_stride, a_comp_stride, record_next_action, gamma, ret_out);
   const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
   return closed_loop_launch(p, io, a, fn, kind, nullptr, pa, {{a_seq_out, a_comp_stride}}, run, PCG_OK, stream);
 }
@@ -574,6 +589,24 @@ int pcg_rollout_policy_pop_unc(pcg_plan* p, const pcg_buffers* io, const pcg_pol
                                int32_t record_next_action, double gamma, double* ret_out, uint64_t seed, void* stream) {
   return pop_rollout(p, io, q, ClosedLoopKind::unc, envs_per_policy, t0, T, a_seq_out, a_step_stride, a_comp_stride, obs_seq,
                      obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, record_next_action, gamma, ret_out, seed, stream);
+}
+
+int pcg_rollout_policy_pop_cons(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q, int64_t envs_per_policy, int32_t t0,
+                                int32_t T, double* a_seq_out, int64_t a_step_stride, int64_t a_comp_stride, double* obs_seq,
+                                int64_t obs_step_stride, int64_t obs_comp_stride, double* rew_seq, int64_t rew_step_stride,
+                                int32_t record_next_action, double* g_seq, int64_t g_step_stride, int64_t g_comp_stride,
+                                uint8_t* viol_seq, int64_t viol_step_stride, double gamma, double* ret_out, int32_t* nviol_out,
+                                double* gmax_out, uint64_t seed, void* stream) {
+  StepArgs a;
+  const void* fn;
+  PCG_TRY(pop_open(p, io, q, ClosedLoopKind::cons, envs_per_policy, gamma, &a, &fn));
+  PopConsArgs pa;
+  pop_head(&pa, q, envs_per_policy, a_seq_out, a_step_stride, a_comp_stride, record_next_action, gamma, ret_out);
+  pa.nviol_out = nviol_out;
+  pa.gmax_out = gmax_out;
+  const ClosedLoopRun run{t0, T, obs_seq, obs_step_stride, obs_comp_stride, rew_seq, rew_step_stride, seed};
+  const ConsRec rec{g_seq, g_step_stride, g_comp_stride, viol_seq, viol_step_stride};
+  return closed_loop_launch(p, io, a, fn, ClosedLoopKind::cons, &rec, pa, {{a_seq_out, a_comp_stride}}, run, PCG_OK, stream);
 }
 
 int pcg_plan_prepare_closed_loop(pcg_plan* p) {

@@ -1220,6 +1220,8 @@ __global__ __launch_bounds__(tb(LDS_STAGES, INTEG, M::NX, ros_structured<M>::val
 #include "pcg_rollout_pop.hpp"
 // (... nor the population forms on plans with per-env parameters)
 #include "pcg_rollout_pop_unc.hpp"
+// (... nor the population forms on plans with constraint rows)
+#include "pcg_rollout_pop_cons.hpp"
 #endif
 namespace pcg {
 
@@ -1230,6 +1232,7 @@ using ActFn = void (*)(const StepArgs, const ActorArgs);
 using PolConsFn = void (*)(const StepArgs, const PolicyArgs, const ConsArgs);
 using ActConsFn = void (*)(const StepArgs, const ActorArgs, const ConsArgs);
 using PopFn = void (*)(const StepArgs, const PopArgs);
+using PopConsFn = void (*)(const StepArgs, const PopConsArgs, const ConsArgs);
 #endif
 
 #ifndef __HIPCC_RTC__
@@ -1292,6 +1295,8 @@ struct Kernels {
   PopFn roll_policy_pop[2];          // roll_policy with one member of a policy population per slice of envs (pcg_rollout_pop.hpp)
   PopFn roll_policy_pop_f32[2];      // ... of a float32 population (pcg_policy_pop_create_f32)
   PopFn roll_policy_pop_unc, roll_policy_pop_unc_f32;  // the population two on plans with per-env parameters (RK4; null for affine: pcg_rollout_pop_unc.hpp)
+  PopConsFn roll_policy_pop_cons[2];      // the population two on plans with constraint rows, with the violation statistics
+  PopConsFn roll_policy_pop_cons_f32[2];  // (pcg_rollout_pop_cons.hpp)
   RhsKFn rhs;
   IntKFn integ[PCG_INT_COUNT][2];
   int nx, na, ndm, nraw;
@@ -1366,6 +1371,10 @@ Kernels make_kernels() {
   k.roll_actor_f32[lean_scheme(PCG_INT_CV8)] = rollout_actor_kernel_f32<M, PCG_INT_CV8>;
   k.roll_policy_cons[lean_scheme(PCG_INT_RK4)] = rollout_cons_policy_kernel<M, PCG_INT_RK4>;
   k.roll_policy_cons[lean_scheme(PCG_INT_CV8)] = rollout_cons_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_policy_pop_cons[lean_scheme(PCG_INT_RK4)] = rollout_pop_cons_policy_kernel<M, PCG_INT_RK4>;
+  k.roll_policy_pop_cons[lean_scheme(PCG_INT_CV8)] = rollout_pop_cons_policy_kernel<M, PCG_INT_CV8>;
+  k.roll_policy_pop_cons_f32[lean_scheme(PCG_INT_RK4)] = rollout_pop_cons_policy_kernel_f32<M, PCG_INT_RK4>;
+  k.roll_policy_pop_cons_f32[lean_scheme(PCG_INT_CV8)] = rollout_pop_cons_policy_kernel_f32<M, PCG_INT_CV8>;
   k.roll_actor_cons[lean_scheme(PCG_INT_RK4)] = rollout_cons_actor_kernel<M, PCG_INT_RK4>;
   k.roll_actor_cons[lean_scheme(PCG_INT_CV8)] = rollout_cons_actor_kernel<M, PCG_INT_CV8>;
   // Tsit5 (the reference's jax method): general kernel, both counter modes, and the integration hook

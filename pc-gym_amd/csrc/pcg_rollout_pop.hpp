@@ -21,8 +21,9 @@
 // A float32 population (pcg_policy_pop_create_f32) is P blocks of pack_policy's float32 form, and rollout_pop_policy_kernel_f32
 // below is the same loop with pcg_rollout_policy_f32.hpp's evaluator: the network in float32, the env, J and disc in fp64.
 //
-// Out of scope: stochastic actors over a population, plans with constraint rows and with run-time compiled code (whose module
-// does not carry these kernels: ahead-of-time only).  Plans with per-env parameters: pcg_rollout_pop_unc.hpp.
+// Out of scope: stochastic actors over a population and plans with run-time compiled code (whose module does not carry these
+// kernels: ahead-of-time only).  Plans with per-env parameters: pcg_rollout_pop_unc.hpp; plans with constraint rows:
+// pcg_rollout_pop_cons.hpp.  These two kernels take neither.
 #pragma once
 
 namespace pcg {

@@ -482,22 +482,47 @@ class VecEnv:
         return self._rollout_population("rollout_policy_pop_unc", pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions,
                                         collect_returns, record_next_action)
 
+    def rollout_population_cons(self, pop, T, envs_per_policy, gamma=1.0, collect_obs=False, collect_rew=False, collect_actions=False,
+                                collect_returns=True, record_next_action=False, collect_g=False, collect_viol=False,
+                                collect_nviol=True, collect_gmax=True):
+        """``rollout_population`` on a plan WITH constraint rows (``pcg_rollout_policy_pop_cons``): the same launch, in which
+        each env computes what ``rollout_policy_cons`` with its member computes, bit for bit (a float32 population: with its
+        float32 member's network).  Returns a dict: "a" (T [+1], na, B), "obs" (T, Nobs, B), "rew" (T, B), "ret" (B,),
+        "g" (T, ncon, B), "viol" (T, B) bool, "nviol" (B,) int32, "gmax" (B,) -- None where not asked for.  "nviol" counts THIS
+        call's steps after which a row was violated (the column sum of "viol") and "gmax" is the largest row value over its
+        steps and rows (the maximum of "g"; from -inf, ``gmax = g if g > gmax else gmax``, so a NaN row leaves it), both kept
+        in registers beside "ret": a constrained search records no T x B flags.  The pre-step check of a call that starts at
+        t = 0 goes to ``env.g_pre`` and counts in neither.  ``env.g`` / ``env.viol`` / ``env.done`` hold the last step afterwards,
+        as after ``rollout_policy_cons``; an env whose ``done`` is set mid-episode keeps stepping.  Plans the kernel does not
+        take (no rows, constraint expressions, user models, per-env parameters, integrators other than rk4 / cv8) raise
+        PcgError."""
+        torch = _torch()
+        nviol = torch.empty(self.B, dtype=torch.int32, device=self.device) if collect_nviol else None
+        gmax, = self._seq_buffers(((self.B,), collect_gmax))
+        out = self._rollout_population("rollout_policy_pop_cons", pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions,
+                                       collect_returns, record_next_action, cons=(collect_g, collect_viol), stats=(_ptr(nviol), _ptr(gmax)))
+        out.update(nviol=nviol, gmax=gmax)
+        return out
+
     def _rollout_population(self, name, pop, T, envs_per_policy, gamma, collect_obs, collect_rew, collect_actions, collect_returns,
-                            record_next_action):
-        """the two ``rollout_population*`` methods: output storage, the call ``pcg_<name>``, the step counter"""
+                            record_next_action, cons=None, stats=()):
+        """the three ``rollout_population*`` methods: output storage, the call ``pcg_<name>``, the step counter.  ``cons`` as in
+        ``_rollout_policy``; ``stats``: what the constrained form takes after ``ret_out``"""
         if self.per_env_t:
             raise ValueError(f"{name.replace('_policy_pop', '_population')}() is lock-stepped only")
         s, dev, B, T = self.spec, self.device, self.B, int(T)
         R = T + (1 if record_next_action else 0)
         a_seq, obs_seq, rew_seq, ret = self._seq_buffers(
             ((R, s.na, B), collect_actions), ((T, s.nobs, B), collect_obs), ((T, B), collect_rew), ((B,), collect_returns))
+        out = {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "ret": ret}
+        rows = self._cons_record(T, cons, out)
         self._buf.d = None
         _lib.check(getattr(self._lib, "pcg_" + name)(
             self._plan, self._bufp, pop.handle(dev), int(envs_per_policy), self.t, T,
             _ptr(a_seq), s.na * B, B, _ptr(obs_seq), s.nobs * B, B, _ptr(rew_seq), B,
-            int(bool(record_next_action)), float(gamma), _ptr(ret), self._episode_seed(), self._stream()), "pcg_" + name)
+            int(bool(record_next_action)), *rows, float(gamma), _ptr(ret), *stats, self._episode_seed(), self._stream()), "pcg_" + name)
         self.t += T
-        return {"a": a_seq, "obs": obs_seq, "rew": rew_seq, "ret": ret}
+        return out
 
     def policy_noise(self, t=None, out=None):
         """z (na, B): the standard normals the fused actor rollout draws at step counter ``t`` (default: the current one) of the

@@ -705,6 +705,17 @@ def fused_pop_unc_ok(spec, pop, envs_per_policy):
             and pop.n_in == spec.nobs and pop.n_out == spec.na and pop.validate() == 0)
 
 
+def fused_pop_cons_ok(spec, pop, envs_per_policy):
+    """the plans, populations and slices pcg_rollout_policy_pop_cons takes (include/pcgym_hip.h): those of
+    pcg_rollout_policy_cons -- affine constraint rows (``ncon``), RK4 / CV8, no per-env parameters, built-in plans only (a
+    constraint expression is run-time compiled: refused) -- with fused_pop_ok's populations and slices: members of the plan's
+    sizes, float64 or float32; slices of whole waves.  ``evaluate_population`` takes the call by default on such a plan."""
+    G = int(envs_per_policy)
+    return (isinstance(pop, PolicyPopulation) and spec.integrator in ("rk4", "cv8") and bool(spec.ncon) and not spec.nunc
+            and not _runtime_compiled(spec) and G >= 64 and G % 64 == 0
+            and pop.n_in == spec.nobs and pop.n_out == spec.na and pop.validate() == 0)
+
+
 def _runtime_compiled(spec):
     """whether the plan of `spec` runs from a run-time compiled module (a user model, a reward or constraint expression)"""
     return bool(spec.user_rhs_src is not None or spec.user_reward_src or spec.user_cons_src)

@@ -27,8 +27,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .policy import (fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_pop_ok,
-                     fused_pop_unc_ok, fused_unc_ok)
+from .policy import (fused_actor_cons_ok, fused_actor_ok, fused_actor_unc_ok, fused_cons_ok, fused_policy_ok, fused_pop_cons_ok,
+                     fused_pop_ok, fused_pop_unc_ok, fused_unc_ok)
 
 
 def _torch():
@@ -204,7 +204,19 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None, fused_
     fused_unc : True takes ``pcg_rollout_policy_pop_unc`` -- one launch as well -- on a built-in RK4 plan with per-env parameters,
     and raises ValueError unless ``fused_pop_unc_ok(spec, pop, envs_per_policy)`` and the env offset is a multiple of 64, or
     together with ``fused=False``.  It has to be asked for: by default such a plan keeps the per-step loop, whose results the
-    fused kernel matches to rounding and not to the bit (the two kernels are compiled separately)."""
+    fused kernel matches to rounding and not to the bit (the two kernels are compiled separately).
+
+    A plan WITH constraint rows takes ONE launch by default as well (``pcg_rollout_policy_pop_cons``, as ``collect_rollouts``
+    takes ``pcg_rollout_policy_cons`` by default) when ``fused_pop_cons_ok`` and the env offset is a multiple of 64;
+    ``fused=False`` keeps the step loop, ``fused=True`` raises ValueError where the launch is not possible (a constraint
+    expression, rows together with per-env parameters, another integrator, slices that are not whole waves).  On such a plan
+    BOTH routes return, beside ``ret`` and ``score``: "nviol" (B,) int32, the number of the episode's steps after which a row
+    was violated; "gmax" (B,), the largest row value over the steps and rows (from -inf, ``gmax = where(g > gmax, g, gmax)``);
+    "viol_share" (P_local,), the mean over each member's envs of ``nviol / T``, sliced as ``score`` is -- what a constrained
+    search forms its fitness from (``score - lam * viol_share``; ``examples/policy_search_constrained.py``).  The launch keeps
+    the three in registers; the step loop forms them in torch from ``env.viol`` / ``env.g``.  On the launch ``ret`` carries
+    the kernel's network arithmetic in place of torch's: the two routes differ through the last bits of the actions alone,
+    as on plans without rows.  A plan without rows returns ``ret`` and ``score`` alone."""
     torch = _torch()
     s = env.spec
     B, G, off = env.B, int(envs_per_policy), int(env.env_offset)
@@ -212,6 +224,9 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None, fused_
         raise ValueError("fused_unc=True asks for the one launch that fused=False declines")
     if fused_unc and not (fused_pop_unc_ok(s, pop, G) and off % 64 == 0):
         raise ValueError("fused_unc: this plan / population / slice size does not qualify for pcg_rollout_policy_pop_unc (fused_pop_unc_ok)")
+    ok_cons = bool(s.ncon) and fused_pop_cons_ok(s, pop, G) and off % 64 == 0
+    if fused and s.ncon and not ok_cons and not fused_unc:
+        raise ValueError("this plan / population / slice size does not qualify for pcg_rollout_policy_pop_cons (fused_pop_cons_ok)")
     if env.per_env_t:
         raise ValueError("evaluate_population needs a lock-stepped VecEnv")
     if pop.n_in != s.nobs or pop.n_out != s.na:
@@ -221,28 +236,45 @@ def evaluate_population(env, pop, envs_per_policy, gamma=1.0, fused=None, fused_
     if not (0.0 <= float(gamma) <= 1.0):
         raise ValueError(f"gamma must be within [0, 1], not {gamma}")
     ok = fused_pop_ok(s, pop, G) and off % 64 == 0
-    if fused and not ok and not fused_unc:
+    if fused and not ok and not ok_cons and not fused_unc:
         raise ValueError("this plan / population / slice size does not qualify for the fused call (fused_pop_ok)")
     T = s.N - 1
     obs, _ = env.reset()
+    nviol = gmax = None
     if fused_unc:  # on request: the reset above sampled the parameters
         ret = env.rollout_population_unc(pop, T, G, gamma=gamma)["ret"]
     elif ok and fused is not False:
         ret = env.rollout_population(pop, T, G, gamma=gamma)["ret"]
+    elif ok_cons and fused is not False:
+        o = env.rollout_population_cons(pop, T, G, gamma=gamma)
+        ret, nviol, gmax = o["ret"], o["nviol"], o["gmax"]
     else:
         ret = torch.zeros(B, dtype=torch.float64, device=env.device)
+        if s.ncon:
+            nviol = torch.zeros(B, dtype=torch.int32, device=env.device)
+            gmax = torch.full((B,), -float("inf"), dtype=torch.float64, device=env.device)
         disc = 1.0
         for _ in range(T):
             obs, rew, _, _, _ = env.step(pop(obs, G, off))
             ret = ret + disc * rew
             disc = disc * float(gamma)
+            if s.ncon:  # the kernel's two statistics of the post-step rows, with its update of gmax, rows ascending
+                nviol += env.viol.to(torch.int32)
+                for row in env.g:
+                    gmax = torch.where(row > gmax, row, gmax)
+
     # the mean over each member's envs: member m holds the envs [m G - off, (m + 1) G - off) of this batch
-    if off % G == 0 and B % G == 0:
-        return {"ret": ret, "score": ret.view(-1, G).mean(dim=1)}
-    m0, m1 = off // G, (off + B - 1) // G
-    bounds = [max(0, m * G - off) for m in range(m0, m1 + 1)] + [B]
-    score = torch.stack([ret[bounds[i]:bounds[i + 1]].mean() for i in range(len(bounds) - 1)])
-    return {"ret": ret, "score": score}
+    def per_member(v):
+        if off % G == 0 and B % G == 0:
+            return v.view(-1, G).mean(dim=1)
+        m0, m1 = off // G, (off + B - 1) // G
+        bounds = [max(0, m * G - off) for m in range(m0, m1 + 1)] + [B]
+        return torch.stack([v[bounds[i]:bounds[i + 1]].mean() for i in range(len(bounds) - 1)])
+
+    out = {"ret": ret, "score": per_member(ret)}
+    if s.ncon:
+        out.update(nviol=nviol, gmax=gmax, viol_share=per_member(nviol.to(torch.float64) / T))
+    return out
 
 
 def centered_ranks(score):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A population of MLP policies in one fused closed-loop launch (pcg_rollout_policy_pop) against what a caller had before it.
 
-    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--dtype float32] [--per-env-params [--members 16,256,4096]] [--out FILE]
+    python tools/population_rollout_bench.py [--B 1048576] [--reps 5] [--shapes affine,1x16,2x64] [--parts 1,2,3] [--dtype float32] [--per-env-params | --constraints [--members 16,256,4096]] [--out FILE]
 
 Workload: the headline's cstr envs (bench.workload_params: RK4, N = 60, dt = 1 s; one episode = 59 closed-loop steps).  All
 routes of a comparison alternate inside one process (`reps` rounds after one warm-up round); times are device-event times
@@ -34,6 +34,18 @@ on B / P envs each, all routes interleaved in one process:
   eval  evaluate_population(fused_unc=True): reset, the one launch, the per-member scores
   a     P times: reset of an env of B / P envs, rollout_policy_unc with member m (rewards recorded), their sum (fp64 only)
   b     evaluate_population(fused=False): one env.step per step with the population's callable form in torch
+
+--constraints measures pcg_rollout_policy_pop_cons (with --dtype float32 its float32 kernel): the workload is the scenario
+cstr_cons_pen_norm under RK4 (N = 60, one affine row family on the temperature, r_penalty), P in --members distinct members on
+B / P envs each, all routes interleaved in one process:
+  new   the population call with ret / nviol / gmax alone (no sequence recorded)
+  c     rollout_population with the same members on cstr_canonical -- the same envs without the rows: what the rows and the
+        two statistics cost
+  d     rollout_policy_cons with ONE policy (member 0) on all envs, nothing recorded (fp64 only: no float32 single-policy form)
+        -- these three from a copied-back start state --
+  eval  evaluate_population: reset, the one launch, scores and violation shares per member
+  a     P times: reset of an env of B / P envs, rollout_policy_cons with member m (rewards and flags recorded), their sums (fp64 only)
+  b     evaluate_population(fused=False): one env.step per step, the statistics formed in torch
 """
 import argparse
 import os
@@ -338,6 +350,94 @@ def unc_rows(a, bench, torch, VecEnv, PolicyPopulation, evaluate_population):
     return lines
 
 
+def cons_rows(a, torch, VecEnv, PolicyPopulation, evaluate_population):
+    import copy
+
+    import scenarios as SC
+
+    p_con = dict(copy.deepcopy(SC.scenarios()["cstr_cons_pen_norm"]["env_params"]), integrator="rk4")
+    p_ref = dict(copy.deepcopy(SC.scenarios()["cstr_canonical"]["env_params"]), integrator="rk4")
+    f64 = a.dtype == "float64"
+    lines = ["# --constraints: cstr_cons_pen_norm under rk4, ms: new = pcg_rollout_policy_pop_cons (ret / nviol / gmax alone), c = "
+             "rollout_population on cstr_canonical (no rows), d = rollout_policy_cons with ONE policy on all envs (nothing recorded); eval = "
+             "evaluate_population, a = P x (reset, rollout_policy_cons, sums) on B / P envs, b = evaluate_population(fused=False)"]
+    kw = dict(activation="tanh", out_map="clip", out_low=-1.0, out_high=1.0, dtype=a.dtype)
+    for name in a.shapes.split(","):
+        for P in [int(v) for v in a.members.split(",")]:
+            G = a.B // P
+            if G < 64 or G % 64:
+                continue
+            big, big2, plain, small = (VecEnv(dict(p_con), n_envs=a.B, seed=1), VecEnv(dict(p_con), n_envs=a.B, seed=1),
+                                       VecEnv(dict(p_ref), n_envs=a.B, seed=1), VecEnv(dict(p_con), n_envs=G, seed=1))
+            spec, T = big.spec, big.spec.N - 1
+            assert spec.ncon >= 1 and not plain.spec.ncon and plain.spec.nobs == spec.nobs and plain.spec.N == spec.N == 60
+            pop = PolicyPopulation(*member_arrays(spec, SHAPES[name], P), **kw)
+            members = [pop.member(m) for m in range(P if f64 else 0)]
+            for q in [pop] + members:
+                q.handle(big.device)
+            starts = {}
+            for e in (big, plain):
+                e.reset()
+                starts[e] = (e.x.clone(), e.obs_soa.clone())
+
+            def restart(e):
+                e.x.copy_(starts[e][0]), e.obs_soa.copy_(starts[e][1])
+                e.t = 0
+
+            def f_new():
+                restart(big)
+                big.rollout_population_cons(pop, T, G)
+
+            def f_c():
+                restart(plain)
+                plain.rollout_population(pop, T, G)
+
+            def f_d():
+                restart(big)
+                big.rollout_policy_cons(members[0], T, collect_rew=False, collect_actions=False, collect_g=False, collect_viol=False)
+
+            keep = {}
+
+            def f_eval():
+                keep["eval"] = evaluate_population(big, pop, G, gamma=1.0)
+
+            def f_a():
+                sc, vs = [], []
+                for q in members:
+                    small.reset()
+                    o = small.rollout_policy_cons(q, T, collect_actions=False, collect_g=False)
+                    sc.append(o["rew"].sum(dim=0).mean()), vs.append(o["viol"].float().mean())
+                keep["a"] = (torch.stack(sc), torch.stack(vs))
+
+            def f_b():
+                keep["b"] = evaluate_population(big2, pop, G, gamma=1.0, fused=False)
+
+            routes = {"new": f_new, "c": f_c, "eval": f_eval, "b": f_b}
+            if f64:
+                routes.update(d=f_d, a=f_a)
+            times = timed(torch, routes, a.reps)
+            med = {k: statistics.median(v) for k, v in times.items()}
+            gap = float((keep["eval"]["score"] - keep["b"]["score"]).abs().max())
+            vgap = float((keep["eval"]["viol_share"] - keep["b"]["viol_share"]).abs().max())
+            row = (f"{name:7s} P={P:5d} G={G:6d}   new {med['new']:9.3f} ({med['new'] / T * 1e3:.1f} us per step)   c {med['c']:9.3f}   "
+                   f"new / c = {med['new'] / med['c']:.3f}")
+            if f64:
+                row += f"   d {med['d']:9.3f}   new / d = {med['new'] / med['d']:.3f}"
+            row += f"   |   eval {med['eval']:9.3f}   b {med['b']:9.3f}   b / eval = {med['b'] / med['eval']:.2f}"
+            if f64:
+                row += f"   a {med['a']:9.3f}   a / eval = {med['a'] / med['eval']:.2f}"
+            lines.append(row + f"   {a.B * T / med['eval'] / 1e-3:.3e} env-steps/s eval   max |score eval - b| {gap:.2e}   "
+                         f"max |viol_share eval - b| {vgap:.2e}   mean viol_share {float(keep['eval']['viol_share'].mean()):.3f}")
+            lines.append("        repeats " + fmt(times))
+            for e in (big, big2, plain, small):
+                e.close()
+            for q in [pop] + members:
+                q.close()
+            del big, big2, plain, small, members, pop, starts
+            torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1 << 20)
@@ -346,7 +446,8 @@ def main():
     ap.add_argument("--parts", help="default: 1,2,3; under --dtype float32: 4")
     ap.add_argument("--dtype", choices=["float64", "float32"], default="float64")
     ap.add_argument("--per-env-params", action="store_true", help="bench.py's cstr_unc: pcg_rollout_policy_pop_unc against what a caller had")
-    ap.add_argument("--members", default="16,256,4096", help="--per-env-params: the population sizes P")
+    ap.add_argument("--constraints", action="store_true", help="cstr_cons_pen_norm: pcg_rollout_policy_pop_cons against what a caller had")
+    ap.add_argument("--members", default="16,256,4096", help="--per-env-params / --constraints: the population sizes P")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch
@@ -369,7 +470,11 @@ def main():
             with open(a.out, "w") as f:
                 f.write(text + "\n")
 
-    if a.per_env_params:
+    if a.constraints:
+        parts = []
+        lines += cons_rows(a, torch, VecEnv, PolicyPopulation, evaluate_population)
+        flush()
+    elif a.per_env_params:
         parts = []
         lines += unc_rows(a, bench, torch, VecEnv, PolicyPopulation, evaluate_population)
         flush()
