@@ -137,7 +137,6 @@ static hipFunction_t jit_head_fn(const pcg_plan* p, const PolicyArgs&) { return 
 static hipFunction_t jit_head_fn(const pcg_plan* p, const ActorArgs&) { return p->jit_act; }
 // (never asked for: pop_open refuses a plan with run-time compiled code, whose module does not carry the population kernels)
 static hipFunction_t jit_head_fn(const pcg_plan*, const PopArgs&) { return nullptr; }
-static hipFunction_t jit_head_fn(const pcg_plan*, const PopConsArgs&) { return nullptr; }
 
 // Plan, buffers and policy handle; then which plans the kind's kernels carry and which kernel it is (`actor`: the head); then
 // the policy's sizes.  *fn stays null for a plan with run-time compiled code, which has no ahead-of-time kernel:
@@ -333,9 +332,8 @@ static int pop_open(pcg_plan* p, const pcg_buffers* io, const pcg_policy_pop* q,
   return PCG_OK;
 }
 
-// what PopArgs and PopConsArgs share
-template <class Args>
-static void pop_head(Args* pa, const pcg_policy_pop* q, int64_t G, double* a_out, int64_t ao_ss, int64_t ao_cs, int32_t record_next,
+// PopArgs, alone or as PopConsArgs' base
+static void pop_head(PopArgs* pa, const pcg_policy_pop* q, int64_t G, double* a_out, int64_t ao_ss, int64_t ao_cs, int32_t record_next,
                      double gamma, double* ret_out) {
   pa->blocks = (const PCG_CONSTANT char*)q->dP;
   pa->stride = (int64_t)(sizeof(double) * q->blob_doubles);

@@ -721,8 +721,8 @@ PCG_DEV void env_pre(const StepArgs& A, CDevConst& c, const double* sched_l, int
   }
 }
 // The three accumulating terms of the declarative tracking reward as exactly specified operation sequences (no contraction),
-// shared by every kernel that states the reward: env_post, env_step_feat (pcg_step_feat.hpp) and env_post_cons
-// (pcg_rollout_cons.hpp).  Under the compiler's default contraction each restatement of `cost += a * b` became an FMA or a
+// shared by every kernel that states the reward: env_post and env_step_feat (pcg_step_feat.hpp; until r26 a third statement,
+// env_post_cons).  Under the compiler's default contraction each restatement of `cost += a * b` became an FMA or a
 // multiply and an add kernel by kernel: rollout_cons_actor_kernel<cstr, RK4> and the feature-masked step kernel gave tracking
 // rewards that differ in the last bit, where pcg_rollout_cons.hpp promises the per-step route's bits.  The order is the
 // oracle's (pcg_oracle.c: one `cost +=` per term).  What these take as arguments -- the normalisations (v - lo) * inv, a
@@ -746,10 +746,16 @@ PCG_DEV double track_box_cost(double cost, double xn, double lon, double hin) {
 }
 
 // ---- second half of make_env.step (pcgym.py:432-498): SP slot, constraints, done, reward, observation ----
-// `x` is the integrated state, `status` what the integrator reported for this env.
-template <class M, bool PER_ENV_T, bool EXTRAS, bool UNC = false>
+// `x` is the integrated state, `status` what the integrator reported for this env.  `Rows` says where the post-step constraint
+// rows come from: StepRows, the rows as pcg_step sums and stores them (constraint_rows into A.g where the plan has any), or a
+// type whose static rows<M>(c, x, spv, dv, u, row_args...) -> "any row > 0" sums and stores them itself (ConsRows,
+// pcg_rollout_cons.hpp).  Its operands travel as trailing arguments, scalars by value: gathered in one struct (by value or by
+// reference alike), or as a pack of forwarding references, the constrained cstr kernels came out with register moves in
+// another order than with env_post restated (profiles/r26/cons_step_refactor.txt).
+struct StepRows {};
+template <class M, bool PER_ENV_T, bool EXTRAS, bool UNC = false, class Rows = StepRows, class... RowArgs>
 PCG_DEV void env_post(const StepArgs& A, CDevConst& c, const double* sched_l, int64_t e, int t, const EnvPre<M>& pre,
-                      const double (&x)[M::NX], int status, EnvOut<M>& out) {
+                      const double (&x)[M::NX], int status, EnvOut<M>& out, RowArgs... row_args) {
   constexpr int NX = M::NX, NA = M::NA;
   const int64_t B = A.B;
   const uint32_t flags = c.flags;
@@ -775,8 +781,13 @@ PCG_DEV void env_post(const StepArgs& A, CDevConst& c, const double* sched_l, in
   const int t_new = t + 1;
   // ---- post-step constraints (pcgym.py:443-446) ----
   bool violated = false;
-  if (EXTRAS && c.ncon > 0) {
-    violated = constraint_rows<M>(c, x, spv, dv, u, A.g, B, e);
+  if constexpr (tt::is_same<Rows, StepRows>::value) {
+    if (EXTRAS && c.ncon > 0) {
+      violated = constraint_rows<M>(c, x, spv, dv, u, A.g, B, e);
+      done |= violated && (flags & PCG_F_DONE_ON_CONS);
+    }
+  } else {
+    violated = Rows::template rows<M>(c, x, spv, dv, u, row_args...);
     done |= violated && (flags & PCG_F_DONE_ON_CONS);
   }
   done |= (t_new == N - 1);  // pcgym.py:448-449

@@ -18,11 +18,13 @@
 // done flag of a step says nothing about the steps after it.  A caller that wants to mask what follows a violation does it
 // from viol_seq.
 //
-// The step is env_pre -> integrate_env -> env_post_cons; env_post_cons restates env_post<M, false, true> with the rows taken
-// from cons_rows (env_step and constraint_rows keep their text; the terms of the tracking reward are the contraction-free
-// track_*_cost of pcg_kernels.hpp in env_post, env_step_feat and here, which is what makes its bits the per-step route's).
-// env_pre's own pre-step check runs with a null g_pre and its verdict is replaced.  The loops are restated and not shared
-// with the unconstrained kernels for the reason pcg_rollout_policy.hpp gives.
+// The step is env_pre -> integrate_env -> env_post<M, false, true>, the per-step route's own second half, with the rows taken
+// from cons_rows through env_post's `Rows` parameter (ConsRows below): set-point slot, done, reward, noise and observation
+// are stated once, in pcg_kernels.hpp (the terms of the tracking reward are its contraction-free track_*_cost, in env_post and
+// env_step_feat alike, which is what makes its bits the per-step route's).  env_pre's own pre-step check runs with a null
+// g_pre and its verdict is replaced.  A kernel that needs the rows in a register beside their stores hands env_step_cons a
+// hook (RowsMax: pcg_rollout_pop_cons.hpp).  The loops are restated and not shared with the unconstrained kernels for the
+// reason pcg_rollout_policy.hpp gives.
 //
 // Out of scope: constraint expressions and user models (their run-time compiled closed-loop module carries the two
 // unconstrained kernels only), float32 networks, per-env parameters, adaptive integrators, and the open-loop pcg_rollout*
@@ -41,12 +43,24 @@ struct ConsArgs {
   int32_t order_w;      // sum the rows in constraint_rows_w's order (the per-step route takes the feature-masked kernel)
 };
 
+// What a kernel does with each post-step row value beside storing it (cons_rows' `See`): nothing ...
+struct RowsUnseen {
+  static PCG_DEV void see(double) {}
+};
+// ... or keeping the largest one.  This statement defines the maximum's bits: a NaN row leaves it unchanged.
+// A hook is a type, and what it keeps travels beside it as trailing reference arguments (`seen`), the way cons_rows_max took
+// `double& gmax` when it was a copy of cons_rows: with the reference held in a hook object passed by value, fourteen
+// population kernels of the large models came out as other code (profiles/r26/cons_step_refactor.txt).
+struct RowsMax {
+  static PCG_DEV void see(double g, double& m) { m = (g > m) ? g : m; }
+};
+
 // constraint rows g = A.[x|sp|d|u] - b of one env in the per-step route's summation order; row r goes to g0[r * s0] and
-// g1[r * s1] (each may be null); returns "any row > 0"
-template <class M>
+// g1[r * s1] (each may be null) and to See::see(g, seen...); returns "any row > 0"
+template <class M, class See = RowsUnseen, class... Seen>
 PCG_DEV bool cons_rows(CDevConst& c, bool order_w, const double (&x)[M::NX], const double (&spv)[PCG_MAX_NSP],
                        const double (&dv)[PCG_MAX_NDM], const double (&u)[M::NA + M::NDM], double* g0, int64_t s0, double* g1,
-                       int64_t s1) {
+                       int64_t s1, Seen&... seen) {
   bool violated = false;
   for (int r = 0; r < c.ncon; ++r) {
     const PCG_CONSTANT double* row = c.con_A[r];
@@ -73,132 +87,29 @@ PCG_DEV bool cons_rows(CDevConst& c, bool order_w, const double (&x)[M::NX], con
     if (g0) g0[(size_t)r * s0] = g;
     if (g1) g1[(size_t)r * s1] = g;
     violated |= (g > 0.0);
+    See::see(g, seen...);
   }
   return violated;
 }
 
-// env_post<M, false, true> (pcgym.py:432-498) with the post-step rows from cons_rows; lock-stepped, built-in plans, no
-// per-env parameters.  Statement by statement env_post's arithmetic.
-template <class M>
-PCG_DEV void env_post_cons(const StepArgs& A, CDevConst& c, const ConsArgs& G, int64_t e, int t, const EnvPre<M>& pre,
-                           const double (&x)[M::NX], int status, double* g0, double* g1, EnvOut<M>& out) {
-  constexpr int NX = M::NX, NA = M::NA;
-  const int64_t B = A.B;
-  const uint32_t flags = c.flags;
-  const int nx = M::DYNAMIC ? c.nx : NX;
-  const int na = M::DYNAMIC ? c.na : NA;
-  const int N = c.N, nsp = c.nsp, nso = c.nsp_obs, nd = c.nd;
-  const int tn = min(t + 1, N - 1);
-  const int tc = min(t, N - 1);
-  const uint64_t env_id = (uint64_t)(A.env_offset + e);
-  const double (&u)[NA + M::NDM] = pre.u;
-  const double (&dv)[PCG_MAX_NDM] = pre.dv;
-  bool done = pre.done_pre;
-  out.status = (uint8_t)status;
-  // ---- SP slot uses SP[t_old] (pcgym.py:432-438, quirk Q5); t += 1 ----
-  double spv[PCG_MAX_NSP] = {0.0, 0.0, 0.0, 0.0};
-  double spn[PCG_MAX_NSP] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nsp) {
-      spv[k] = sched_at<false>(A.sched, nullptr, false, k, N, tc);
-      spn[k] = sched_at<false>(A.sched, nullptr, false, k, N, tn);
-    }
-  const int t_new = t + 1;
-  // ---- post-step constraints (pcgym.py:443-446) ----
-  const bool violated = cons_rows<M>(c, G.order_w != 0, x, spv, dv, u, g0, G.g_cs, g1, B);
-  done |= violated && (flags & PCG_F_DONE_ON_CONS);
-  done |= (t_new == N - 1);  // pcgym.py:448-449
-  out.done = done;
-  out.viol = violated;
-  // ---- reward on the noise-free state (pcgym.py:470-482) ----
-  double r = 0.0;
-  if (flags & PCG_F_REWARD_BATCH) {  // pcgym.py:502-532
-    if (t_new == N - 1) {
-      for (int k = 0; k < c.nrew; ++k) {
-        const double v = pick<NX>(x, c.rew_index[k]) * c.r_scale[k];
-        r = (flags & PCG_F_MAXIMISE) ? r + v : r - v;
-      }
-      if ((flags & PCG_F_R_PENALTY) && violated) r -= 1000.0;
-    }
-  } else {  // pcgym.py:535-558
-#pragma unroll
-    for (int k = 0; k < PCG_MAX_NSP; ++k)
-      if (k < nsp) {
-        const double dd = pick<NX>(x, c.sp_index[k]) - spn[k];
-        r += (-(dd * dd)) * c.r_scale[k];
-        if ((flags & PCG_F_R_PENALTY) && violated) r -= 1000.0;  // Q4: once per SP key
-      }
+// env_post's `Rows` for these kernels: the post-step rows from cons_rows.  What cons_rows needs beside the step's values comes
+// as env_post's trailing arguments (pcg_kernels.hpp says why they are not members of this type).
+template <class See>
+struct ConsRows {
+  template <class M, class... Seen>
+  static PCG_DEV bool rows(CDevConst& c, const double (&x)[M::NX], const double (&spv)[PCG_MAX_NSP], const double (&dv)[PCG_MAX_NDM],
+                           const double (&u)[M::NA + M::NDM], bool order_w, double* g0, int64_t s0, double* g1, int64_t s1,
+                           Seen&... seen) {
+    return cons_rows<M, See>(c, order_w, x, spv, dv, u, g0, s0, g1, s1, seen...);
   }
-  out.rew = r;
-  // ---- observation: noise (pcgym.py:452-466), normalise (:483-489), mask (:495-498) ----
-  double zn[NX];
-  if (flags & PCG_F_NOISE) {
-#pragma unroll
-    for (int i = 0; i < NX; i += 2) {
-      double z0, z1;
-      rng_normal2(A.seed, env_id, (uint32_t)t, RNG_NOISE + (uint32_t)(i >> 1), z0, z1);
-      zn[i] = z0;
-      if (i + 1 < NX) zn[i + 1] = z1;
-    }
-  }
-  double on[NX];  // physical observation of the states, noise included
-#pragma unroll
-  for (int i = 0; i < NX; ++i) {
-    on[i] = 0.0;
-    if (i < nx) {
-      double o = x[i];
-      if (flags & PCG_F_NOISE) o += zn[i] * x[i] * c.noise_pct[i];
-      on[i] = o;
-      out.ox[i] = (o - c.omap[i].lo) * c.omap[i].sc + c.omap[i].off;
-    }
-  }
-  if (flags & PCG_F_REWARD_TRACK) {  // the declarative tracking reward, as in env_post
-    double cost = 0.0;
-#pragma unroll
-    for (int k = 0; k < PCG_MAX_NSP; ++k)
-      if (k < nsp) {
-        double xv = pick<NX>(on, c.sp_index[k]);
-        if constexpr (tt::is_same<M, Model<PCG_MODEL_CRYST>>::value) {
-          if (flags & PCG_F_REWARD_CRYST) {  // cryst_train.py:24-25: CV and Ln from the observed moments
-            if (c.sp_index[k] == 5) xv = sqrt(on[2] * on[0] / (on[1] * on[1]) - 1.0);
-            if (c.sp_index[k] == 6) xv = on[1] / on[0];
-          }
-        }
-        const double xn = (xv - c.trk_lo[k]) * c.trk_inv[k];
-        const double sn = (spn[k] - c.trk_lo[k]) * c.trk_inv[k];
-        cost = track_sp_cost(cost, xn, sn, c.r_scale[k]);
-      }
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-      if (j < na) {
-        const double up0 = A.u_prev[(size_t)j * B + e];
-        const double up = (up0 == up0) ? up0 : u[j];  // NaN: no previous action yet
-        const double un = (u[j] - c.act_lo[j]) * c.act_inv[j];
-        const double upn = (up - c.act_lo[j]) * c.act_inv[j];
-        cost = track_act_cost(cost, c.R_du, c.R_u, un, upn);
-        A.u_prev[(size_t)j * B + e] = u[j];
-      }
-    if (violated)
-      for (int q = 0; q < c.nbox; ++q) {
-        const double xn = (pick<NX>(on, c.box_index[q]) - c.box_lo[q]) * c.box_inv[q];
-        cost = track_box_cost(cost, xn, c.box_lon[q], c.box_hin[q]);
-      }
-    out.rew = -cost;
-  }
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NSP; ++k)
-    if (k < nso) out.osp[k] = (spv[k] - c.omap[nx + k].lo) * c.omap[nx + k].sc + c.omap[nx + k].off;
-#pragma unroll
-  for (int k = 0; k < PCG_MAX_NDM; ++k)
-    if (k < nd) out.od[k] = (dv[k] - c.omap[nx + nso + k].lo) * c.omap[nx + nso + k].sc + c.omap[nx + nso + k].off;
-}
+};
 
 // one env step of a constrained plan: env_step<M, INTEG, false, false, true> with cons_rows in both constraint checks.
-// g0 / g1: where this step's rows go (the sequence's row s, io->g on the last step), each may be null.
-template <class M, int INTEG>
+// g0 / g1: where this step's rows go (the sequence's row s, io->g on the last step), each may be null; `See` is shown the
+// post-step rows alone: the pre-step check at counter 0 is no step of the call.
+template <class M, int INTEG, class See = RowsUnseen, class... Seen>
 PCG_DEV void env_step_cons(const StepArgs& A, CDevConst& c, const ConsArgs& G, int64_t e, int t, const double (&a_in)[M::NA],
-                           double (&x)[M::NX], double* g0, double* g1, EnvOut<M>& out) {
+                           double (&x)[M::NX], double* g0, double* g1, EnvOut<M>& out, Seen&... seen) {
   constexpr int NX = M::NX;
   const int nx = M::DYNAMIC ? c.nx : NX;
   typename M::CKP& kp = model_kp<M>(c);
@@ -212,7 +123,9 @@ PCG_DEV void env_step_cons(const StepArgs& A, CDevConst& c, const ConsArgs& G, i
     pre.done_pre = v && (c.flags & PCG_F_DONE_ON_CONS);
   }
   const int status = integrate_env<M, INTEG, false>(A, c, kp, pre.u, x, nullptr, e, nx);
-  env_post_cons<M>(A, c, G, e, t, pre, x, status, g0, g1, out);
+  // (RowArgs spelled out: deduced, the by-value pack would copy what `seen` refers to)
+  env_post<M, false, true, false, ConsRows<See>, bool, double*, int64_t, double*, int64_t, Seen&...>(
+      A, c, nullptr, e, t, pre, x, status, out, G.order_w != 0, g0, G.g_cs, g1, A.B, seen...);
 }
 
 // rollout_policy_kernel's loop (pcg_rollout_policy.hpp) on a plan with constraint rows
